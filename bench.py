@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py — co-occurrence nonzeros/sec of the GloVe training step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload text8_d64] [--batch-size B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload text8_d64] [--batch-size B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs exactly W warm-up steps, times exactly K steps (one region between device synchronisations:
+`ms_per_step` = its time / K), writes what the last step computed if `--dump-outputs` is given, and prints the result
+line.  The inputs are seeded, so the same arguments step the same batches from the same tables on every run, and two
+builds can be compared output for output.  Everything else below — the per-kernel pass and `roofline`, `cpu_baseline`,
+the other configurations — runs only under `--full`.
 
 A "step" is one optimizer step over one batch of B synthetic co-occurrence nonzeros that are already resident in HBM.
 On one GPU the stream is stepped the way the trainer steps it by default (`--epoch-shuffle full`, what the reference's
@@ -13,8 +19,8 @@ builds on a side stream, steps replayed from hipGraphs).  `--static-index` times
 N = 1: the sparse Adagrad step (fused forward+gradient pass kernel(s) + apply kernel; glove_step_adagrad_f32 picks the
 form).  The headline is the workload BASELINE.json's metric is quoted on at 1, 2, 4 and 8 GPUs — config 4, synthetic
 Zipf V = 400 k, d = 300 — as the one-GPU shard of its 200 M nonzeros (25 M, batches of 1 M): the configuration where
-"achieved HBM GB/s vs peak" is about HBM (text8's tables live in the caches).  Unless `--single` is given the run also
-times the other configurations (each a `[bench-config]` line on stderr): text8 d = 64 (BASELINE configs[1]: static index, index rebuilt every step, the
+"achieved HBM GB/s vs peak" is about HBM (text8's tables live in the caches).  With `--full`, unless `--single` is given,
+the run also times the other configurations (each a `[bench-config]` line on stderr): text8 d = 64 (BASELINE configs[1]: static index, index rebuilt every step, the
 reference's batch size, Keras-legacy Adam), V = 50 k at d = 300 and V = 2 M at d = 128, each with its own roofline —
 as far as the wall-clock budget (`--budget-seconds`) goes; what did not fit is named in `configs_skipped`.  `roofline.frac`
 of every entry = algorithmic bytes per step / ms_per_step / 8 TB/s (the whole step as timed, index work included).
@@ -28,10 +34,11 @@ the other configurations (stderr lines, bench_configs.json): the same with a sta
 BASELINE.json words it (dense-gradient all-reduce or touched-rows all-gather, whichever is the shorter payload), config 5
 sharded in both modes.
 
-Rank 0 prints ONE JSON line — the headline alone, a few KB, the last thing on stdout; every other configuration is a
-`[bench-config] {...}` line on stderr and an entry of bench_configs.json (gpurun_out/ when it exists).  `roofline` is measured live with HIP events on the
-launch stream in a second, instrumented pass over the same batches; `cpu_baseline` times the C port of the oracle
-(oracle/glove_ref.c: all cores with OpenMP, and one core) on a bounded sample.
+Rank 0 prints ONE JSON line — the headline alone, a few KB, the last thing on stdout.  With `--full` every other
+configuration is a `[bench-config] {...}` line on stderr and an entry of bench_configs.json (see write_configs_file);
+`roofline` is measured live with HIP events on the launch stream in a second, instrumented pass over the same batches;
+`cpu_baseline` times the C port of the oracle (oracle/glove_ref.c: all cores with OpenMP, and one core) on a bounded
+sample.
 """
 from __future__ import annotations
 
@@ -107,11 +114,17 @@ def parse(argv=None):
     ap.add_argument("--single", action="store_true", help="only the named workload (no configs[] array)")
     ap.add_argument("--with-configs", action="store_true", help="the configs[] array also under --rehearse-on-one-gpu")
     ap.add_argument("--min-timed-ms", type=float, default=20.0,
-                    help="the timed region of --steps steps is repeated until this much time has been measured; the "
-                         "median repeat is reported")
+                    help="--full's other configurations: the timed region of a configuration's steps is repeated until this "
+                         "much time has been measured; the median repeat is reported")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="control-flow rehearsal of the multi-rank path on a one-GPU box: every rank uses cuda:0 and the "
                          "collectives go through gloo; its numbers mean nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: the per-kernel pass and roofline, the CPU baseline, "
+                         "the other configurations (configs[], bench_configs.json); without it a run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last step computed (loss, a fixed sample of the trained rows "
+                         "and their optimizer slots) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -343,11 +356,25 @@ def steps_per_graph(steps: int) -> int:
 def timed_region(ctx, run, steps, warmup, min_timed_ms):
     """The contract's timed region around run(n_steps): warm-up, then exactly `steps` steps between barrier + synchronize on
     both sides, MAX over ranks; repeated at least three times and until at least min_timed_ms have been measured (a single
-    transient cannot swing the figure), median reported.  Returns (median seconds, all)."""
+    transient cannot swing the figure), median reported.  Returns (median seconds, all).
+    min_timed_ms None (the headline): exactly `warmup` steps, then ONE region of exactly `steps` steps — a run's step count
+    is then fixed by its arguments, and so is what its last step computes (--dump-outputs)."""
     dev, world, dist = ctx.dev, ctx.world, ctx.dist
     torch.cuda.synchronize()
     log("  warm-up steps")
     run(warmup)
+    if min_timed_ms is None:
+        log("  timed region")
+        ctx.barrier()
+        t0 = time.perf_counter()
+        run(steps)
+        ctx.barrier()
+        el = time.perf_counter() - t0
+        if world > 1:
+            stop = torch.tensor([el], dtype=torch.float64, device=dev)
+            dist.all_reduce(stop, op=dist.ReduceOp.MAX)
+            el = float(stop[0].item())
+        return el, [el]
     # the first tens of milliseconds after the load phase run slow whatever the kernels are (B = 1 M at text8 scale:
     # 158 us/step in a first region of 200 steps, 47 in every later one; a graph's first replay also carries its
     # upload): the warm-up goes on, untimed, until the loop has run for 50 ms
@@ -395,8 +422,46 @@ def event_us(fn, reps=3, stream=None):
     return sorted(spans)[len(spans) // 2]
 
 
+DUMP_ROWS = 4096          # rows of each table side in --dump-outputs: Adam at d = 300 writes 6 x 4096 x 300 x 4 B = 29.5 MB
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, tables, loss_out):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy files — the loss vector
+    (loss, L, Reg, sum_e), and of both tables the weights, biases and optimizer slots (DeviceTables.state_dict's names) on a
+    fixed sample of DUMP_ROWS rows per side (seeded: the same ids every run; a whole C4 table is 480 MB)."""
+    import numpy as np
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    gen = torch.Generator(device="cpu")
+    pick = {}
+    for side, rows in (("row", tables.V_row), ("col", tables.V_col)):
+        gen.manual_seed(0)                      # (both sides of a V x V model: the same ids)
+        ids = torch.randperm(rows, generator=gen)[:DUMP_ROWS] if rows > DUMP_ROWS else torch.arange(rows)
+        pick[side] = ids.sort().values.to(tables.device)
+
+    def rows(x, ids):
+        x = x.index_select(0, ids)
+        return x[:, :tables.d_model] if x.dim() == 2 else x
+    tables.canonicalize()                       # a twinned or tagged table back in its plain form, as state_dict() reads it
+    arrays = {"loss": loss_out}
+    for n in tables.NAMES:
+        ids = pick["row" if n in ("R", "br") else "col"]
+        arrays[n] = rows(getattr(tables, n), ids)
+        for slot, d in (("slot1_", tables.s1), ("slot2_", tables.s2)):
+            if n in d:
+                arrays[slot + n] = rows(d[n], ids)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes > %d" % (total, DUMP_MAX_BYTES))
+    for k, a in host.items():
+        np.save(out / (k + ".npy"), a)
+    log("  outputs of the last step: %d arrays, %.1f MB in %s" % (len(host), total / 1e6, out))
+
+
 def run_dealt_multi(ctx, workload, B, mode, steps=200, warmup=20, lr=0.05, chunk_cap=0, step_form=0, exchange="auto",
-                    no_graph=False, min_timed_ms=20.0, segment=0):
+                    no_graph=False, min_timed_ms=20.0, segment=0, full=True, dump=""):
     """The multi-rank forms in the trainer's default mode (--epoch-shuffle full), set up as trainer.estimator sets them up:
     every rank deals ITS shard anew every epoch (NonzeroStream + ReshufflingRunner over the form's stepper); with both tables
     sharded the epoch's fetch lists are agreed between the ranks beside the steps.  mode: "dp", "rowsharded", "sharded"."""
@@ -450,9 +515,50 @@ def run_dealt_multi(ctx, workload, B, mode, steps=200, warmup=20, lr=0.05, chunk
             done += runner.run(n_steps - done)
     elapsed, elapsed_all = timed_region(ctx, run, steps, warmup, min_timed_ms)
     final_loss = float(stepper.loss_out[0].item())
-    log("  %.4f ms per step (%d repeats); per-phase pass" % (elapsed / steps * 1e3, len(elapsed_all)))
+    log("  %.4f ms per step (%d repeats)" % (elapsed / steps * 1e3, len(elapsed_all)))
     if not (final_loss == final_loss):
         raise SystemExit("loss is NaN")
+    if dump and rank == 0:
+        dump_outputs(dump, tables, stepper.loss_out)
+    rows = getattr(stepper, "rows", False)
+    parallelism = {"dp": "dp%d, %s" % (world, "touched-rows all-gather" if rows else "dense-grad all-reduce"),
+                   "sharded": "both tables sharded x%d, touched col rows by all-to-all" % world,
+                   "rowsharded": "row table sharded x%d, col side %s" % (
+                       world, "local (one rank)" if world == 1 else "touched-rows all-gather" if rows else "dense all-reduce")}[mode]
+    out = {
+        "metric": "co-occurrence nonzeros/sec", "value": steps * B * world / elapsed, "unit": "nonzeros/s",
+        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+        "repeats": len(elapsed_all), "ms_per_step_min_max": [min(elapsed_all) / steps * 1e3, max(elapsed_all) / steps * 1e3],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": DATA_NOTE.get(workload, "synthetic"),
+        "config": {"workload": workload, "V": V, "d": d, "optimizer": "Adagrad",
+                   "batch_size_per_gpu": B, "global_batch": B * world, "nnz_per_gpu": nnz, "batches_per_epoch": nb, "chunk_cap": runner.cap,
+                   **({"rehearsal": "ranks share cuda:0 over gloo: control flow only, the numbers mean nothing"}
+                      if ctx.args.rehearse_on_one_gpu else {}),
+                   "index": "rebuilt every step: every rank deals its shard anew every epoch (trainer.stepper.ReshufflingRunner over the "
+                            "form's stepper), indexes and fetch lists prepared beside the steps, inside the timed region",
+                   "launch": "the trainer's runner, steps launched eagerly (collectives on the transport's stream)",
+                   "parallelism": parallelism,
+                   "exchange_floats_per_rank_per_step": getattr(stepper, "payload_floats", None)},
+        "masters_build_ms_at_load": masters_ms, "final_loss": final_loss,
+    }
+    if full:
+        log("  per-phase pass")
+        full_dealt_multi(ctx, out, run, runner, stepper, B, d, elapsed / steps)
+    runner.release_graphs()
+    if hasattr(stepper, "release_graphs"):
+        stepper.release_graphs()
+    del runner, stream, tables, stepper
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    log("  done: %.3g nonzeros/s, %.4f ms per step" % (out["value"], out["ms_per_step"]))
+    return out
+
+
+def full_dealt_multi(ctx, out, run, runner, stepper, B, d, step_s):
+    """--full, after run_dealt_multi's timed region: the phases of one step apart (each timed to its end, collectives
+    included) and the roofline, into `out`."""
+    dev, dist, world = ctx.dev, ctx.dist, ctx.world
     torch.cuda.synchronize()
     # ---- what the batches touched, and the phases of one step apart (each timed to its end, collectives included)
     if runner.sharded:
@@ -495,52 +601,23 @@ def run_dealt_multi(ctx, workload, B, mode, steps=200, warmup=20, lr=0.05, chunk
     step_us = sum(kern.values())
     # per GPU, like the peak it is held against: one rank's share of the job's step (the mean over the ranks' batches)
     alg = 16 * B + 16 * (d + 1) * (u_row_all + u_col_all) / world
-    achieved = alg / (elapsed / steps) / 1e9
-    rows = getattr(stepper, "rows", False)
-    parallelism = {"dp": "dp%d, %s" % (world, "touched-rows all-gather" if rows else "dense-grad all-reduce"),
-                   "sharded": "both tables sharded x%d, touched col rows by all-to-all" % world,
-                   "rowsharded": "row table sharded x%d, col side %s" % (
-                       world, "local (one rank)" if world == 1 else "touched-rows all-gather" if rows else "dense all-reduce")}[mode]
+    achieved = alg / step_s / 1e9
     peak = HBM_PEAK_GBS
-    out = {
-        "metric": "co-occurrence nonzeros/sec", "value": steps * B * world / elapsed, "unit": "nonzeros/s",
-        "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-        "repeats": len(elapsed_all), "ms_per_step_min_max": [min(elapsed_all) / steps * 1e3, max(elapsed_all) / steps * 1e3],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": DATA_NOTE.get(workload, "synthetic"),
-        "config": {"workload": workload, "V": V, "d": d, "optimizer": "Adagrad",
-                   "batch_size_per_gpu": B, "global_batch": B * world, "nnz_per_gpu": nnz, "batches_per_epoch": nb, "chunk_cap": runner.cap,
-                   **({"rehearsal": "ranks share cuda:0 over gloo: control flow only, the numbers mean nothing"}
-                      if ctx.args.rehearse_on_one_gpu else {}),
-                   "index": "rebuilt every step: every rank deals its shard anew every epoch (trainer.stepper.ReshufflingRunner over the "
-                            "form's stepper), indexes and fetch lists prepared beside the steps, inside the timed region",
-                   "launch": "the trainer's runner, steps launched eagerly (collectives on the transport's stream)",
-                   "parallelism": parallelism,
-                   "exchange_floats_per_rank_per_step": getattr(stepper, "payload_floats", None)},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
-                     "frac": achieved / peak, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
-                     "stream_ceiling": HBM_STREAM_GBS, "traffic": None,
-                     "traffic_source": "multi-rank form: not profiled with counters", "traffic_over_algorithmic": None,
-                     "kernel": "per GPU; one step = " + " + ".join(kern),
-                     "algorithmic_bytes_per_step": alg, "kernel_us": kern,
-                     "step_kernels_alone_frac": alg / (step_us * 1e-6) / 1e9 / peak,
-                     "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks},
-        "masters_build_ms_at_load": masters_ms, "final_loss": final_loss,
-    }
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s",
+                       "frac": achieved / peak, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
+                       "stream_ceiling": HBM_STREAM_GBS, "traffic": None,
+                       "traffic_source": "multi-rank form: not profiled with counters", "traffic_over_algorithmic": None,
+                       "kernel": "per GPU; one step = " + " + ".join(kern),
+                       "algorithmic_bytes_per_step": alg, "kernel_us": kern,
+                       "step_kernels_alone_frac": alg / (step_us * 1e-6) / 1e9 / peak,
+                       "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks}
     out["collectives"] = collectives_breakdown(kern)
     out["process_group"] = process_group_facts(ctx)
-    runner.release_graphs()
-    if hasattr(stepper, "release_graphs"):
-        stepper.release_graphs()
-    del runner, stream, tables, plans, items, stepper
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    log("  done: %.3g nonzeros/s, %.1f us per step of phases, roofline %.3f" % (out["value"], step_us, out["roofline"]["frac"]))
-    return out
+    log("  %.1f us per step of phases, roofline %.3f" % (step_us, out["roofline"]["frac"]))
 
 
 def run_dealt(ctx, workload, B, optimizer="Adagrad", steps=200, warmup=20, lr=0.05, chunk_cap=0, step_form=0,
-              no_graph=False, min_timed_ms=20.0, segment=0):
+              no_graph=False, min_timed_ms=20.0, segment=0, full=True, dump=""):
     """One GPU, the trainer's default mode (--epoch-shuffle full): the stream object and the runner are the trainer's own
     (trainer.data_utils.NonzeroStream, trainer.stepper.ReshufflingRunner), timed from outside — epoch deals, index builds
     and steps all inside the timed region."""
@@ -579,9 +656,44 @@ def run_dealt(ctx, workload, B, optimizer="Adagrad", steps=200, warmup=20, lr=0.
             done += runner.run(n_steps - done)
     elapsed, elapsed_all = timed_region(ctx, run, steps, warmup, min_timed_ms)
     final_loss = float(runner.loss_out[0].item())
-    log("  %.4f ms per step (%d repeats); per-kernel pass" % (elapsed / steps * 1e3, len(elapsed_all)))
+    log("  %.4f ms per step (%d repeats)" % (elapsed / steps * 1e3, len(elapsed_all)))
     if not (final_loss == final_loss):
         raise SystemExit("loss is NaN")
+    if dump:
+        dump_outputs(dump, tables, runner.loss_out)
+    out = {
+        "metric": "co-occurrence nonzeros/sec", "value": steps * B / elapsed, "unit": "nonzeros/s",
+        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
+        "repeats": len(elapsed_all), "ms_per_step_min_max": [min(elapsed_all) / steps * 1e3, max(elapsed_all) / steps * 1e3],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": DATA_NOTE.get(workload, "synthetic"),
+        "config": {"workload": workload, "V": V, "d": d, "optimizer": optimizer,
+                   "batch_size_per_gpu": B, "global_batch": B, "nnz_per_gpu": nnz, "batches_per_epoch": nb, "chunk_cap": cap,
+                   "index": "rebuilt every step: epochs dealt from the sorted master orders (one partition pass per epoch), the "
+                            "index of %d consecutive batches numbered by %d launches on a side stream, inside the timed region%s" % (
+                                S, 3 if runner.records else 2,
+                                "" if runner.records else "; no chunk records: run words, pair fields %s the epoch's arrays" % (
+                                    "borrowed from" if getattr(runner, "borrow", False) else "copied from")),
+                   "launch": "the trainer's runner: steps replayed from hipGraphs of 2^k steps" if runner.graphs_on else
+                             "the trainer's runner: every run of steps issued by one C call (glove_steps_adagrad_f32)",
+                   "parallelism": "single GPU", "chunk_records": bool(runner.records), "chunk_run_words": bool(getattr(runner, "run_words", False))},
+        "masters_build_ms_at_load": masters_ms, "final_loss": final_loss,
+    }
+    if full:
+        log("  per-kernel pass")
+        full_dealt(ctx, out, runner, stream, B, V, d, adam, workload, elapsed / steps)
+    runner.release_graphs()
+    del runner, stream, tables
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    log("  done: %.3g nonzeros/s, %.4f ms per step" % (out["value"], out["ms_per_step"]))
+    return out
+
+
+def full_dealt(ctx, out, runner, stream, B, V, d, adam, workload, step_s):
+    """--full, after run_dealt's timed region: what the batches touched, the pieces of a step apart and the roofline, into
+    `out`."""
+    hip, nb, S = ctx.hip, runner.nb, runner.S
     # ---- what the batches touched (the staging plans of both slots, as the last builds left them)
     torch.cuda.synchronize()
     plans = [p for blk in runner.slots for p in blk.plans]
@@ -613,48 +725,25 @@ def run_dealt(ctx, workload, B, optimizer="Adagrad", steps=200, warmup=20, lr=0.
     kern["epoch_deal"] = event_us(lambda: hip.deal_epoch(stream.masters, B, 12345, spare[0], spare[1], stream._deal_ws),
                                   stream=stream.side) / nb
     alg = algorithmic_bytes_adam(B, V, d) if adam else algorithmic_bytes(B, d, u_row, u_col)
-    achieved = alg / (elapsed / steps) / 1e9
+    achieved = alg / step_s / 1e9
     traffic, traffic_src = measured_traffic(workload, B, "dealt") if not adam else (None, "Adam: not profiled with counters")
-    out = {
-        "metric": "co-occurrence nonzeros/sec", "value": steps * B / elapsed, "unit": "nonzeros/s",
-        "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": elapsed / steps * 1e3,
-        "repeats": len(elapsed_all), "ms_per_step_min_max": [min(elapsed_all) / steps * 1e3, max(elapsed_all) / steps * 1e3],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": DATA_NOTE.get(workload, "synthetic"),
-        "config": {"workload": workload, "V": V, "d": d, "optimizer": optimizer,
-                   "batch_size_per_gpu": B, "global_batch": B, "nnz_per_gpu": nnz, "batches_per_epoch": nb, "chunk_cap": cap,
-                   "index": "rebuilt every step: epochs dealt from the sorted master orders (one partition pass per epoch), the "
-                            "index of %d consecutive batches numbered by %d launches on a side stream, inside the timed region%s" % (
-                                S, 3 if runner.records else 2,
-                                "" if runner.records else "; no chunk records: run words, pair fields %s the epoch's arrays" % (
-                                    "borrowed from" if getattr(runner, "borrow", False) else "copied from")),
-                   "launch": "the trainer's runner: steps replayed from hipGraphs of 2^k steps" if runner.graphs_on else
-                             "the trainer's runner: every run of steps issued by one C call (glove_steps_adagrad_f32)",
-                   "parallelism": "single GPU", "chunk_records": bool(runner.records), "chunk_run_words": bool(getattr(runner, "run_words", False))},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
-                     "stream_ceiling": HBM_STREAM_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_over_algorithmic": (traffic / alg) if traffic else None,
-                     "kernel": "one step as timed = step kernels, beside them on a side stream index_build and epoch_deal",
-                     "algorithmic_bytes_per_step": alg, "kernel_us": kern,
-                     "kernel_us_note": "per step, each piece alone on an idle GPU (HIP events on its launch stream); in the timed "
-                                       "region index_build and epoch_deal overlap the steps",
-                     "step_kernels_alone_frac": alg / (kern["step"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                     "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks},
-        "masters_build_ms_at_load": masters_ms, "final_loss": final_loss,
-    }
-    runner.release_graphs()
-    del kg, runner, stream, tables, plans
-    torch.cuda.synchronize()
-    torch.cuda.empty_cache()
-    log("  done: %.3g nonzeros/s, %.4f ms per step, roofline %.3f (step kernels alone %.1f us, index %.1f us, deal %.1f us per step)" % (
-        out["value"], out["ms_per_step"], out["roofline"]["frac"], kern["step"], kern["index_build"], kern["epoch_deal"]))
-    return out
+    out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
+                       "stream_ceiling": HBM_STREAM_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                       "traffic_over_algorithmic": (traffic / alg) if traffic else None,
+                       "kernel": "one step as timed = step kernels, beside them on a side stream index_build and epoch_deal",
+                       "algorithmic_bytes_per_step": alg, "kernel_us": kern,
+                       "kernel_us_note": "per step, each piece alone on an idle GPU (HIP events on its launch stream); in the timed "
+                                         "region index_build and epoch_deal overlap the steps",
+                       "step_kernels_alone_frac": alg / (kern["step"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                       "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks}
+    log("  roofline %.3f (step kernels alone %.1f us, index %.1f us, deal %.1f us per step)" % (
+        out["roofline"]["frac"], kern["step"], kern["index_build"], kern["epoch_deal"]))
 
 
 def run_config(ctx, workload, B, optimizer="Adagrad", mode="auto", steps=200, warmup=20, lr=0.05, chunk_cap=0,
                step_form=0, exchange="auto", dynamic=False, no_graph=False, max_batches=64,
-               min_timed_ms=20.0, segment=0):
+               min_timed_ms=20.0, segment=0, full=True, dump=""):
     """mode: "auto" (single-GPU sparse step on one rank, data parallel on several), "dp" (data-parallel form also on
     one rank), "sharded" (both tables sharded), "rowsharded" (row table sharded, col side data parallel)."""
     from trainer.hip_api import FUSED_STEP_BYTES, DeviceTables, auto_chunk_cap, make_hyper, row_width
@@ -666,9 +755,11 @@ def run_config(ctx, workload, B, optimizer="Adagrad", mode="auto", steps=200, wa
     if adam and mode != "single":
         raise SystemExit("--optimizer Adam is benchmarked on one GPU")
     if dynamic and mode == "single":
-        return run_dealt(ctx, workload, B, optimizer, steps, warmup, lr, chunk_cap, step_form, no_graph, min_timed_ms, segment)
+        return run_dealt(ctx, workload, B, optimizer, steps, warmup, lr, chunk_cap, step_form, no_graph, min_timed_ms, segment,
+                         full, dump)
     if dynamic:
-        return run_dealt_multi(ctx, workload, B, mode, steps, warmup, lr, chunk_cap, step_form, exchange, no_graph, min_timed_ms, segment)
+        return run_dealt_multi(ctx, workload, B, mode, steps, warmup, lr, chunk_cap, step_form, exchange, no_graph, min_timed_ms,
+                               segment, full, dump)
     log("%s B=%d %s mode=%s: generating the workload" % (workload, B, optimizer, mode))
     wl = ctx.workload(workload)
     V, d = wl["V"], wl["d"]
@@ -803,94 +894,11 @@ def run_config(ctx, workload, B, optimizer="Adagrad", mode="auto", steps=200, wa
 
     elapsed, elapsed_all = timed_region(ctx, lambda n: run(n, 0), steps, warmup, min_timed_ms)
     final_loss = float(loss_out[0].item())
-    log("  %.4f ms per step (%d repeats); per-kernel pass" % (elapsed / steps * 1e3, len(elapsed_all)))
+    log("  %.4f ms per step (%d repeats)" % (elapsed / steps * 1e3, len(elapsed_all)))
     if not (final_loss == final_loss):
         raise SystemExit("loss is NaN")
-
-    # ---- instrumented pass: HIP events (on the launch stream) around `reps` back-to-back launches of
-    # each piece of the step over the same resident batches; per-launch time = span / reps (it includes
-    # the ~1-2 us launch-to-launch gap that rocprofv3's per-kernel durations exclude)
-    reps = max(min(nb, 8), min(200, steps))
-    if stepper is not None:
-        calls = dict(stepper.phases())
-        items = handles
-    else:
-        items = plans
-        form = step_form
-        calls = {}
-        if adam:
-            adam_fused = 2 * B <= V_row + V          # glove_step_adam_f32's own rule (include/glove_hip.h)
-            one_launch = adam_fused and tables.R_tag is not None and B <= 2048 and plans[0].r_mark is not None and form in (0, 5)
-            if one_launch:
-                # twinned tables, plans with id bitmaps: the whole step is ONE kernel (+ a one-workgroup epilogue)
-                calls["step_adam_one_launch"] = lambda p: hip.step_adam(p, tables, hyper, G, loss_out, ws)
-            else:
-                calls["passes"] = lambda p: hip.passes(p, tables, hyper, ws)
-            if one_launch:
-                pass
-            elif adam_fused:
-                # passes (+ id marks) and ONE fused apply/decay kernel; the second kernel has no entry point of its own,
-                # so it is timed as the whole step minus the passes
-                calls["step_adam"] = lambda p: hip.step_adam(p, tables, hyper, G, loss_out, ws)
-            else:
-                calls["dense_grad"] = lambda p: hip.dense_grad(p, tables, hyper, G, ws)
-                calls["dense_adam"] = lambda p: hip.dense_adam(tables, hyper, G, loss_out)
-        else:
-            fused_auto = plans[0].fusable and (u_row + u_col) * tables.d * 16 >= FUSED_STEP_BYTES
-            if form == 0:
-                form = 5 if tables.R_tag is not None and B <= 2048 else (4 if tables.R_ver is not None else 3) if fused_auto else 1
-            if form == 1 or not plans[0].fusable:
-                calls["passes"] = lambda p: hip.passes(p, tables, hyper, ws)      # row side + col side, one launch
-                calls["apply_adagrad"] = lambda p: hip.apply_adagrad(p, tables, hyper, loss_out, ws)
-            else:
-                # the fused forms have no entry points per launch: the step is timed whole (rocprofv3 splits it:
-                # profiles/*_kernel_stats.txt)
-                calls["step_fused_form_%d" % form] = lambda p: hip.step_adagrad(p, tables, hyper, loss_out, ws)
-    kern = {}
-    finish = getattr(stepper, "finish_async", None)
-    if finish is not None:
-        # a phase that only STARTS a collective (the sharded forms overlap it with the row side) is timed to its end here
-        calls = {name: (lambda x, fn=fn: (fn(x), finish())) for name, fn in calls.items()}
-    for name, fn in calls.items():
-        for i in range(min(2 * nb, 8)):
-            fn(items[i % nb])
-        torch.cuda.synchronize()
-
-        def burst(fn=fn):
-            for i in range(reps):
-                fn(items[i % nb])
-        if mode == "single":                  # replayed from a hipGraph, so that a kernel shorter than the host's
-            kg = torch.cuda.CUDAGraph()       # per-call cost (small batches) is still timed on the GPU's clock
-            with torch.cuda.graph(kg):
-                burst()
-            burst = kg.replay
-            burst()
-        spans = []
-        for _ in range(3):                    # median of three spans: robust against a transient on a fresh box
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            burst()
-            b.record()
-            torch.cuda.synchronize()
-            spans.append(a.elapsed_time(b) * 1e3 / reps)
-        kern[name] = sorted(spans)[1]
-    if "step_adam" in kern:
-        kern["adam_fused"] = kern.pop("step_adam") - kern["passes"]
-    # attribution of the algorithmic bytes to the two kernels of the two-launch sparse step: the pass
-    # kernel owns the nonzero stream and ONE read of every distinct row + bias; the apply kernel owns the accumulator
-    # read and the two writes
-    per_kernel = None
-    if stepper is None and not adam and "apply_adagrad" in kern:
-        attributed = {"passes": 16 * B + 4 * (d + 1) * (u_row + u_col), "apply_adagrad": 12 * (d + 1) * (u_row + u_col)}
-        per_kernel = {k: {"algorithmic_bytes": attributed[k], "avg_us": kern[k],
-                          "achieved_GBps": attributed[k] / (kern[k] * 1e-6) / 1e9,
-                          "frac": attributed[k] / (kern[k] * 1e-6) / 1e9 / HBM_PEAK_GBS} for k in attributed}
-    step_us = sum(kern.values())
-    alg = algorithmic_bytes_adam(B, V, d) if adam else algorithmic_bytes(B, d, u_row, u_col)
-    # the whole step as timed (contract: bytes / ms_per_step); the kernels alone, back to back, are reported beside it
-    achieved = alg / (elapsed / steps) / 1e9
-    traffic, traffic_src = measured_traffic(workload, B, "static") if mode == "single" and not adam else \
-        (None, "Adam: not profiled with counters" if adam else "multi-rank form: not profiled with counters")
+    if dump and rank == 0:
+        dump_outputs(dump, tables, loss_out)
     rows = getattr(stepper, "rows", False)
     parallelism = {"single": "single GPU",
                    "dp": "dp%d, %s" % (world, "touched-rows all-gather" if rows else "dense-grad all-reduce"),
@@ -912,23 +920,110 @@ def run_config(ctx, workload, B, optimizer="Adagrad", mode="auto", steps=200, wa
                    "launch": "hipGraph replay, %d steps per graph" % spg if graph is not None else "eager",
                    "parallelism": parallelism,
                    **({"exchange_floats_per_rank_per_step": getattr(stepper, "payload_floats", None)} if stepper is not None else {})},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
-                     "stream_ceiling": HBM_STREAM_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_over_algorithmic": (traffic / alg) if traffic else None,
-                     "kernel": "one step = " + " + ".join(kern),
-                     "algorithmic_bytes_per_step": alg, "kernel_us": kern, "per_kernel": per_kernel,
-                     "step_kernels_alone_frac": alg / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                     "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks},
         "plan_build_ms_per_batch": plan_build_ms, "final_loss": final_loss,
     }
-    if stepper is not None:
-        out["collectives"] = collectives_breakdown(kern)
-        out["process_group"] = process_group_facts(ctx)
+    if full:
+        log("  per-kernel pass")
+        # ---- instrumented pass: HIP events (on the launch stream) around `reps` back-to-back launches of
+        # each piece of the step over the same resident batches; per-launch time = span / reps (it includes
+        # the ~1-2 us launch-to-launch gap that rocprofv3's per-kernel durations exclude)
+        reps = max(min(nb, 8), min(200, steps))
+        if stepper is not None:
+            calls = dict(stepper.phases())
+            items = handles
+        else:
+            items = plans
+            form = step_form
+            calls = {}
+            if adam:
+                adam_fused = 2 * B <= V_row + V          # glove_step_adam_f32's own rule (include/glove_hip.h)
+                one_launch = adam_fused and tables.R_tag is not None and B <= 2048 and plans[0].r_mark is not None and form in (0, 5)
+                if one_launch:
+                    # twinned tables, plans with id bitmaps: the whole step is ONE kernel (+ a one-workgroup epilogue)
+                    calls["step_adam_one_launch"] = lambda p: hip.step_adam(p, tables, hyper, G, loss_out, ws)
+                else:
+                    calls["passes"] = lambda p: hip.passes(p, tables, hyper, ws)
+                if one_launch:
+                    pass
+                elif adam_fused:
+                    # passes (+ id marks) and ONE fused apply/decay kernel; the second kernel has no entry point of its own,
+                    # so it is timed as the whole step minus the passes
+                    calls["step_adam"] = lambda p: hip.step_adam(p, tables, hyper, G, loss_out, ws)
+                else:
+                    calls["dense_grad"] = lambda p: hip.dense_grad(p, tables, hyper, G, ws)
+                    calls["dense_adam"] = lambda p: hip.dense_adam(tables, hyper, G, loss_out)
+            else:
+                fused_auto = plans[0].fusable and (u_row + u_col) * tables.d * 16 >= FUSED_STEP_BYTES
+                if form == 0:
+                    form = 5 if tables.R_tag is not None and B <= 2048 else (4 if tables.R_ver is not None else 3) if fused_auto else 1
+                if form == 1 or not plans[0].fusable:
+                    calls["passes"] = lambda p: hip.passes(p, tables, hyper, ws)      # row side + col side, one launch
+                    calls["apply_adagrad"] = lambda p: hip.apply_adagrad(p, tables, hyper, loss_out, ws)
+                else:
+                    # the fused forms have no entry points per launch: the step is timed whole (rocprofv3 splits it:
+                    # profiles/*_kernel_stats.txt)
+                    calls["step_fused_form_%d" % form] = lambda p: hip.step_adagrad(p, tables, hyper, loss_out, ws)
+        kern = {}
+        finish = getattr(stepper, "finish_async", None)
+        if finish is not None:
+            # a phase that only STARTS a collective (the sharded forms overlap it with the row side) is timed to its end here
+            calls = {name: (lambda x, fn=fn: (fn(x), finish())) for name, fn in calls.items()}
+        for name, fn in calls.items():
+            for i in range(min(2 * nb, 8)):
+                fn(items[i % nb])
+            torch.cuda.synchronize()
+
+            def burst(fn=fn):
+                for i in range(reps):
+                    fn(items[i % nb])
+            if mode == "single":                  # replayed from a hipGraph, so that a kernel shorter than the host's
+                kg = torch.cuda.CUDAGraph()       # per-call cost (small batches) is still timed on the GPU's clock
+                with torch.cuda.graph(kg):
+                    burst()
+                burst = kg.replay
+                burst()
+            spans = []
+            for _ in range(3):                    # median of three spans: robust against a transient on a fresh box
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                burst()
+                b.record()
+                torch.cuda.synchronize()
+                spans.append(a.elapsed_time(b) * 1e3 / reps)
+            kern[name] = sorted(spans)[1]
+        if "step_adam" in kern:
+            kern["adam_fused"] = kern.pop("step_adam") - kern["passes"]
+        # attribution of the algorithmic bytes to the two kernels of the two-launch sparse step: the pass
+        # kernel owns the nonzero stream and ONE read of every distinct row + bias; the apply kernel owns the accumulator
+        # read and the two writes
+        per_kernel = None
+        if stepper is None and not adam and "apply_adagrad" in kern:
+            attributed = {"passes": 16 * B + 4 * (d + 1) * (u_row + u_col), "apply_adagrad": 12 * (d + 1) * (u_row + u_col)}
+            per_kernel = {k: {"algorithmic_bytes": attributed[k], "avg_us": kern[k],
+                              "achieved_GBps": attributed[k] / (kern[k] * 1e-6) / 1e9,
+                              "frac": attributed[k] / (kern[k] * 1e-6) / 1e9 / HBM_PEAK_GBS} for k in attributed}
+        step_us = sum(kern.values())
+        alg = algorithmic_bytes_adam(B, V, d) if adam else algorithmic_bytes(B, d, u_row, u_col)
+        # the whole step as timed (contract: bytes / ms_per_step); the kernels alone, back to back, are reported beside it
+        achieved = alg / (elapsed / steps) / 1e9
+        traffic, traffic_src = measured_traffic(workload, B, "static") if mode == "single" and not adam else \
+            (None, "Adam: not profiled with counters" if adam else "multi-rank form: not profiled with counters")
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_stream_ceiling": achieved / HBM_STREAM_GBS,
+                           "stream_ceiling": HBM_STREAM_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                           "traffic_over_algorithmic": (traffic / alg) if traffic else None,
+                           "kernel": "one step = " + " + ".join(kern),
+                           "algorithmic_bytes_per_step": alg, "kernel_us": kern, "per_kernel": per_kernel,
+                           "step_kernels_alone_frac": alg / (step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                           "heavy_ids_per_step": n_heavy, "uniq_rows_per_step": u_row, "uniq_cols_per_step": u_col, "chunks_per_step": chunks}
+        if stepper is not None:
+            out["collectives"] = collectives_breakdown(kern)
+            out["process_group"] = process_group_facts(ctx)
+        log("  %.1f us per step of kernels, roofline %.3f" % (step_us, out["roofline"]["frac"]))
     del tables, plans, handles, batches, stepper, graph
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
-    log("  done: %.3g nonzeros/s, %.1f us per step of kernels, roofline %.3f" % (out["value"], step_us, out["roofline"]["frac"]))
+    log("  done: %.3g nonzeros/s, %.4f ms per step" % (out["value"], out["ms_per_step"]))
     return out
 
 
@@ -956,7 +1051,6 @@ def config_line(r: dict) -> dict:
 def headline(out: dict) -> dict:
     """The ONE stdout line: the headline configuration only, a few KB at most (a driver keeps the tail of stdout — every
     other configuration goes to stderr as `[bench-config]` lines and, whole, to bench_configs.json)."""
-    rf = out["roofline"]
     cfg = {k: out["config"][k] for k in ("workload", "V", "d", "optimizer", "batch_size_per_gpu", "global_batch", "nnz_per_gpu",
                                          "chunk_cap", "parallelism", "rehearsal", "same_workload_static_index",
                                          "exchange_floats_per_rank_per_step") if k in out["config"]}
@@ -966,10 +1060,12 @@ def headline(out: dict) -> dict:
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                 "scaling", "vs_baseline", "dtype", "data") if k in out}
     line["config"] = cfg
-    line["roofline"] = {k: rf[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
-                                           "traffic_over_algorithmic", "algorithmic_bytes_per_step", "kernel",
-                                           "step_kernels_alone_frac", "frac_of_measured_stream_ceiling") if k in rf}
-    line["roofline"]["kernel_us"] = {k: round(v, 2) for k, v in rf["kernel_us"].items()}
+    if "roofline" in out:
+        rf = out["roofline"]
+        line["roofline"] = {k: rf[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
+                                               "traffic_over_algorithmic", "algorithmic_bytes_per_step", "kernel",
+                                               "step_kernels_alone_frac", "frac_of_measured_stream_ceiling") if k in rf}
+        line["roofline"]["kernel_us"] = {k: round(v, 2) for k, v in rf["kernel_us"].items()}
     cb = out.get("cpu_baseline")
     if cb is not None:
         line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "sample", "host_cpus", "usable_cores",
@@ -1006,14 +1102,16 @@ def write_configs_file(out: dict) -> str:
     return ""
 
 
-def emit_headline(out: dict, rank: int) -> None:
-    """Rank 0: the headline as a `[bench-config]` stderr line, the side file, and THE stdout line (the only JSON line there)."""
+def emit_headline(out: dict, rank: int, full: bool) -> None:
+    """Rank 0: THE stdout line (the only JSON line there); with --full before it the headline as a `[bench-config]` stderr
+    line and the side file."""
     if rank != 0:
         return
-    out["name"] = "headline"
-    print("[bench-config] " + json.dumps(config_line(out)), file=sys.stderr, flush=True)
-    out["configs_file"] = write_configs_file(out)
-    sys.stderr.flush()
+    if full:
+        out["name"] = "headline"
+        print("[bench-config] " + json.dumps(config_line(out)), file=sys.stderr, flush=True)
+        out["configs_file"] = write_configs_file(out)
+        sys.stderr.flush()
     print(json.dumps(headline(out)), flush=True)
 
 
@@ -1073,20 +1171,20 @@ def main(argv=None):
     hip = hip_api.GloveHip(dev)
     ctx = Ctx(args, world, rank, dev, dist, hip)
     common = dict(lr=args.learning_rate, chunk_cap=args.chunk_cap, step_form=args.step_form, exchange=args.exchange,
-                  no_graph=args.no_graph, max_batches=args.max_batches, min_timed_ms=args.min_timed_ms)
+                  no_graph=args.no_graph, max_batches=args.max_batches)
     B_head = args.batch_size or DEFAULT_BATCH[args.workload]
     big = args.workload in ("zipf_v400k_d300", "zipf_v2m_d128")
     if mode == "auto" and world > 1 and big and args.exchange == "auto":
         mode = "sharded"        # the form whose exchange follows the batch, not the vocabulary (DESIGN.md "Multi-GPU")
-    out = run_config(ctx, args.workload, B_head, args.optimizer, mode, args.steps, args.warmup,
-                     dynamic=not args.static_index, segment=args.index_segment, **common)
-    plain = not (args.single or args.static_index or args.index_segment or args.optimizer != "Adagrad" or args.row_sharded or args.force_dense or
+    out = run_config(ctx, args.workload, B_head, args.optimizer, mode, args.steps, args.warmup, min_timed_ms=None,
+                     dynamic=not args.static_index, segment=args.index_segment, full=args.full, dump=args.dump_outputs, **common)
+    side_configs = args.full and not (args.single or args.static_index or args.index_segment or args.optimizer != "Adagrad" or args.row_sharded or args.force_dense or
                  args.step_form or args.chunk_cap or args.batch_size or args.workload != "zipf_v400k_d300" or
                  (args.rehearse_on_one_gpu and not args.with_configs))
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and mode == "auto":
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and mode == "auto":
         log("cpu baseline (%g s)" % args.cpu_seconds)
         out["cpu_baseline"] = cpu_baseline(ctx, ctx.workload(args.workload), B_head, args.learning_rate, args.cpu_seconds)
-    if plain:
+    if side_configs:
         # the other configurations of BASELINE.json / BASELINE.md §3 in the same line, the HBM-bound ones last (the tail of
         # a long line is what a log keeps).  (name, estimated seconds incl. load, run_config arguments)
         extra = dict(lr=args.learning_rate, max_batches=8, min_timed_ms=args.min_timed_ms, exchange=args.exchange)
@@ -1120,7 +1218,7 @@ def main(argv=None):
             # no run of this path on more than one GPU exists: the headline is on stdout before any side
             # configuration starts, so nothing that happens in one of them can take it away
             out["wall_seconds"] = time.perf_counter() - T_START
-            emit_headline(out, rank)
+            emit_headline(out, rank, args.full)
         configs, skipped, failed = [], [], []
         for name, est, spec in specs:
             # the decision is rank 0's (the ranks' clocks differ) and collective
@@ -1156,11 +1254,11 @@ def main(argv=None):
                 out["config"]["same_workload_static_index"] = {
                     "nonzeros_per_s": r["value"], "ms_per_step": r["ms_per_step"], "index": r["config"]["index"]}
     out.setdefault("wall_seconds", time.perf_counter() - T_START)
-    if world > 1 and plain:
+    if world > 1 and side_configs:
         if rank == 0:
             write_configs_file(out)             # (the stdout line went out before the side configurations)
     else:
-        emit_headline(out, rank)
+        emit_headline(out, rank, args.full)
     faulthandler.cancel_dump_traceback_later()
     if dist is not None:
         import gc

@@ -348,6 +348,33 @@ def test_bench_headline_is_one_short_line(world):
         assert len(json.dumps(bench.config_line(r))) < 1024
 
 
+def test_bench_dump_outputs_is_a_fixed_sample_within_64_mb(tmp_path):
+    """bench.dump_outputs (--dump-outputs): float32 .npy files of the loss and of every table, bias and optimizer slot, on
+    the same seeded sample of rows every call (row and col sides alike), within 64 MB for Adam at d = 300."""
+    import sys
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+    import bench
+    from trainer.hip_api import DeviceTables
+    V, d = 10000, 300
+    t = DeviceTables(V, d, "Adam", device="cpu", seed=0)
+    ids = torch.arange(V, dtype=torch.float32)
+    t.br, t.bc = ids.clone(), ids.clone()
+    t.s1["R"][:, 0] = ids
+    loss = torch.tensor([1.5, 1.25, 0.25, 3.0])
+    for name in ("a", "b"):
+        bench.dump_outputs(tmp_path / name, t, loss)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"loss", "R", "C", "br", "bc"} | {s + n for s in ("slot1_", "slot2_") for n in ("R", "C", "br", "bc")}
+    assert all(a.dtype == np.float32 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    rows = got["br"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and (np.diff(rows) > 0).all() and rows[-1] < V
+    assert (got["bc"] == got["br"]).all() and (got["slot1_R"][:, 0] == got["br"]).all()
+    assert got["R"].shape == (bench.DUMP_ROWS, d) and (got["R"] == t.R[rows, :d].numpy()).all()
+    assert (got["loss"] == loss.numpy()).all()
+    for f in (tmp_path / "b").glob("*.npy"):
+        assert (np.load(f) == got[f.stem]).all(), f.stem
+
+
 def test_bench_traffic_table_points_at_committed_profiles():
     """bench.TRAFFIC_PROFILES: every row names a committed PMC summary of that very configuration (workload, batch, index
     mode in the file's own meta), and a configuration without a row says why its traffic is null."""

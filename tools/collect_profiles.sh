@@ -12,7 +12,7 @@ out=gpurun_out/profiles_$tag
 raw=gpurun_out/raw_${tag}_$name
 mkdir -p $out $raw
 export TMPDIR=/tmp
-B="python3 bench.py --single --no-cpu-baseline --workload $wl --batch-size $batch $extra"
+B="python3 bench.py --full --single --no-cpu-baseline --workload $wl --batch-size $batch $extra"
 psteps=$(( steps < 40 ? steps : 40 ))
 echo "[$name] kernel trace"; date
 rocprofv3 --kernel-trace --stats --output-format csv -d $raw/stats -- $B --steps $steps --warmup 10 > $raw/stats.log 2>&1 || { tail -5 $raw/stats.log; exit 1; }

@@ -2,8 +2,8 @@
 # Runs on the GPU box: the bench lines behind DESIGN.md §6 (one log per row under gpurun_out/table/).
 out=gpurun_out/table
 rm -rf $out; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 400 python bench.py --single --no-cpu-baseline "$@" > $out/$name.log 2>&1 || echo "$name FAILED"; }
-timeout -k 10 600 python bench.py > $out/default.log 2>&1 || echo "default FAILED"
+run() { name=$1; shift; timeout -k 10 400 python bench.py --full --single --no-cpu-baseline "$@" > $out/$name.log 2>&1 || echo "$name FAILED"; }
+timeout -k 10 600 python bench.py --full > $out/default.log 2>&1 || echo "default FAILED"
 run b1024 --workload text8_d64 --batch-size 1024 --steps 4000 --warmup 200
 run b1m --workload text8_d64 --batch-size 1048576
 run adam1024 --workload text8_d64 --optimizer Adam --batch-size 1024 --steps 4000 --warmup 200 --learning-rate 0.001
