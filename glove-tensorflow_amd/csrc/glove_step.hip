@@ -1042,6 +1042,9 @@ __device__ inline void sum_blockpart(const float *blockpart, int nblocks, float 
 __device__ inline void loss_from_partials(const float (&tot)[kPartials], const StepConsts &k, float g,
                                           float &loss, float &L, float &reg)
 {
+    // (no contraction: left to the compiler, the products fused differently in different epilogues — the touched-rows exchange
+    // reported Adamax's and Nadam's loss a few bits away from the single-GPU step's on the same partials)
+#pragma clang fp contract(off)
     // tot = {sum w diff^2, sum |r|^2+|c|^2, sum br^2+bc^2, sum e}
     L = tot[0] * k.inv_batch;
     reg = k.l2 * k.inv_d * k.inv_batch * tot[1] + k.l2 * k.inv_batch * tot[2] + k.l2 * g * g;

@@ -94,7 +94,9 @@ typedef struct glove_hyper {
      * both summed over the batch and divided by the batch size. */
     int32_t head;
     float neg_factor;           /* --neg-factor; read by the logistic head only */
-    /* form of glove_step_adagrad_f32 / glove_steps_adagrad_f32 (same result bit for bit in every form):
+    /* form of glove_step_adagrad_f32 / glove_steps_adagrad_f32.  The forms agree bit for bit except in the order in which
+     * the pairs of an id of several chunks are summed: the fused and tagged forms may therefore differ from the two-launch
+     * form in the last bits (every form is bitwise repeatable):
      *   GLOVE_STEP_AUTO                the library chooses from the plan's id counts and the row width
      *   GLOVE_STEP_TWO_LAUNCH          passes (both sides) -> apply: every chunk's sums travel through a partial row
      *   GLOVE_STEP_FUSED_ONE_PASS      (tests and A/B comparisons only) both sides in one launch, every finished row through
@@ -120,7 +122,8 @@ typedef struct glove_hyper {
      *                                  launch behind it does the once-per-step scalars (global bias, loss, global_step).  Ids of
      *                                  up to heavy_chunks chunks come out bit-identical to the two-launch form, the others
      *                                  within fp32 rounding of their sums' order.  Needs chunk records.  AUTO picks it for
-     *                                  batches of at most 2,048 pairs when the tables carry tags. */
+     *                                  batches of at most 2,048 pairs when the tables carry tags — on a plan refilled on the
+     *                                  device (host_counts[4] < 0) even when the batch holds an id of more chunks. */
     int32_t step_form;
     /* which Keras optimizer glove_step_sparse_f32 applies (reference src/models/train_utils.py:13-16 resolves any Keras name
      * with `tf.keras.optimizers.get`, handing over the learning rate only: everything else keeps its Keras-legacy default):
@@ -454,14 +457,15 @@ int glove_step_sparse_f32(const glove_plan *plan, const glove_tables *t, const g
 /* One Keras-legacy Adam step.  G_flat (glove_dense_grad_layout floats, all zero on entry) is scratch and is all zero
  * again on return.  A batch of at most (V_row + V) / 2 pairs takes two launches: the passes also mark the batch's
  * ids (in G_flat's bias segments), then one kernel applies the marked ids and gives every other row the G = 0
- * update; larger batches run passes + glove_dense_grad_f32 + glove_dense_adam_f32.  Same result bit for bit.
+ * update; larger batches run passes + glove_dense_grad_f32 + glove_dense_adam_f32.  These two agree bit for bit.
  * ONE launch (glove_hyper.step_form AUTO or GLOVE_STEP_TAGGED) when both tables are twinned (glove_tables.R_tag / C_tag
  * non-NULL: R, br hold 2 x V_row rows / entries, C, bc 2 x V; the tags themselves stay zero), the plan carries chunk records
  * and id bitmaps (r_mark / c_mark) and the batch has at most 2,048 pairs and touches a minority of the rows: every row of
  * both tables moves from the current copy to the other one — the batch's rows by the lane group that holds the id's first
  * chunk (gradient, then Adam), all others by a sweep that skips the bitmaps' ids; scalars[3] says which copy is current
  * (glove_canonicalize_f32 copies the second copies home; every other entry point calls it first).  Swept rows and ids of
- * up to heavy_chunks chunks bit-identical to the two-launch form, the others within fp32 rounding of their sums' order. */
+ * up to heavy_chunks chunks bit-identical to the two-launch form, the others within fp32 rounding of their sums' order —
+ * AUTO takes this form for a plan refilled on the device (host_counts[4] < 0) even when its batch holds such an id. */
 int glove_step_adam_f32(const glove_plan *plan, const glove_tables *t, const glove_hyper *h,
                         void *ws, size_t ws_bytes, float *G_flat, float *loss_out, void *stream);
 /* n consecutive Keras-legacy Adam steps from one host call; G_flat is left zeroed after every step.  Consecutive steps that

@@ -80,6 +80,79 @@ def assert_tables_close(dt, t, rtol=1e-5, atol=1e-6):
     assert dt.global_step == t.step
 
 
+# the oracle's slot prefixes of every Keras optimizer, in the order of the device slots s1, s2 (glove_tables s1_*, s2_*)
+SLOTS = {"Adagrad": ("A_",), "Adam": ("M_", "V_"), "SGD": ("A_",), "RMSprop": ("A_",), "Adamax": ("M_", "V_"),
+         "Adadelta": ("A_", "U_"), "Ftrl": ("A_", "Z_"), "Nadam": ("M_", "V_")}
+
+
+def slot_padding(optimizer: str, k: int) -> float:
+    """What the padding columns of slot k (0 = s1) hold from DeviceTables on: Adagrad's and Ftrl's accumulators 0.1, all else 0."""
+    return 0.1 if k == 0 and optimizer in ("Adagrad", "Ftrl") else 0.0
+
+
+def opt_tables_from_oracle(t: "ref.Tables", DeviceTables, device="cuda:0"):
+    """Device tables holding exactly the (fp32-rounded) oracle state of any of the eight optimizers: the parameters, every
+    slot, the global bias with its slots, global_step, and Nadam's momentum cache in scalars[4 + step % 2] — the slot the
+    next step reads; the other one, which that step writes before anything reads it, holds NaN."""
+    dt = DeviceTables(t.V, t.d, t.optimizer, device=device, seed=0)
+    f = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(device)
+    dm = dt.d_model
+    slots = SLOTS[t.optimizer]
+
+    def put(dst, a):
+        (dst[:, :dm] if dst.dim() == 2 else dst).copy_(f(a))
+    for n in ("R", "C", "br", "bc"):
+        put(getattr(dt, n), getattr(t, n))
+        for k, pre in enumerate(slots):
+            put((dt.s1, dt.s2)[k][n], getattr(t, pre + n))
+    sc = np.zeros(8, np.float32)
+    sc[0] = t.g
+    for k, pre in enumerate(slots):
+        sc[1 + k] = getattr(t, pre + "g")
+    if t.optimizer == "Nadam":
+        sc[4 + t.step % 2], sc[4 + (t.step + 1) % 2] = t.m_cache, np.nan
+    dt.scalars.copy_(torch.from_numpy(sc))
+    dt.step.fill_(t.step)
+    return dt
+
+
+def _assert_close_on_device(got, want, rtol, atol, what):
+    """assert_allclose(got, want) for a device tensor against a float64 array, compared on the device (the tables of a
+    large vocabulary are hundreds of MB); NaN never passes.  The host comparison runs only to report a failure."""
+    w = torch.from_numpy(np.ascontiguousarray(want, np.float64)).to(got.device)
+    ok = (got.double() - w).abs() <= atol + rtol * w.abs()
+    if not bool(ok.all()):
+        np.testing.assert_allclose(got.cpu().numpy(), want, rtol=rtol, atol=atol, err_msg=what)
+        raise AssertionError("%s: %d entries outside rtol %g / atol %g" % (what, int((~ok).sum()), rtol, atol))
+
+
+def assert_opt_tables_close(dt, t, rtol=1e-5, atol=1e-6):
+    """Every variable and slot of any of the eight optimizers against the oracle; the padding columns of R and C exactly zero,
+    those of every slot exactly at their initial value; the global bias and its slots, Nadam's momentum cache, global_step."""
+    dm = dt.d_model
+    slots = SLOTS[t.optimizer]
+    logical = lambda x: x[:, :dm] if x.dim() == 2 else x
+    for n in ("R", "C", "br", "bc"):
+        x = getattr(dt, n)
+        _assert_close_on_device(logical(x), getattr(t, n), rtol, atol, n)
+        if x.dim() == 2 and dt.d > dm:
+            assert float(x[:, dm:].abs().max()) == 0.0, n + " padding moved"
+        for k, pre in enumerate(slots):
+            s = (dt.s1, dt.s2)[k][n]
+            a = 1e-9 if t.optimizer == "Adam" and pre == "V_" else atol         # (Adam's v: squares of small gradients)
+            _assert_close_on_device(logical(s), getattr(t, pre + n), rtol, a, pre + n)
+            if s.dim() == 2 and dt.d > dm:
+                assert bool((s[:, dm:] == slot_padding(t.optimizer, k)).all()), pre + n + " padding moved"
+    sc = dt.scalars.cpu().numpy().astype(np.float64)
+    np.testing.assert_allclose(sc[0], t.g, rtol=rtol, atol=atol, err_msg="global_bias")
+    for k, pre in enumerate(slots):
+        a = 1e-9 if t.optimizer == "Adam" and pre == "V_" else atol
+        np.testing.assert_allclose(sc[1 + k], getattr(t, pre + "g"), rtol=rtol, atol=a, err_msg=pre + "g")
+    if t.optimizer == "Nadam":
+        np.testing.assert_allclose(sc[4 + t.step % 2], t.m_cache, rtol=rtol, err_msg="momentum cache")
+    assert dt.global_step == t.step
+
+
 def free_port() -> int:
     """A TCP port nobody listens on right now (for a torch.distributed rendezvous on 127.0.0.1): fixed numbers derived from the
     pid fell into the ephemeral range and collided, once in a while, with a connection of an earlier test."""
