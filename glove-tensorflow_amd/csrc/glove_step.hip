@@ -1379,7 +1379,8 @@ __device__ inline void nadam_elem(float &w, float &m, float &v, float g, const N
 // used by the apply epilogues of the single-GPU step (SparseOptApply) and of the touched-rows exchange (apply_packed_kernel)
 struct OptConsts { float lr, eps, momentum, lr_t, b1, b2; int nesterov; float rho; };
 template <int OPT> struct OptSlots {
-    static constexpr bool two = OPT == GLOVE_OPT_ADAMAX || OPT == GLOVE_OPT_ADADELTA || OPT == GLOVE_OPT_FTRL || OPT == GLOVE_OPT_NADAM;
+    static constexpr bool two = OPT == GLOVE_OPT_ADAMAX || OPT == GLOVE_OPT_ADADELTA || OPT == GLOVE_OPT_FTRL || OPT == GLOVE_OPT_NADAM ||
+                                OPT == GLOVE_OPT_ADAM;
 };
 template <int OPT>
 struct OptElem {
@@ -1415,13 +1416,23 @@ struct OptElem {
         v = fmaxf(o.b2 * v, fabsf(g));
         w -= o.lr_t * m / (v + o.eps);
     }
-    // (nk: Nadam's constants of this step — the touched-rows exchange only: apply_packed_kernel; a = m, b = v)
+    // RMSprop as dense_rmsprop_kernel spells it (a = rms): the entry's rms takes (1 - rho) g^2, the weight moves where g != 0
+    __device__ static void rmsprop(float &w, float &a, float g, const OptConsts &o)
+    {
+#pragma clang fp contract(off)
+        a = o.rho * a + (1.0f - o.rho) * g * g;
+        if (g != 0.f) w -= o.lr * g / (sqrtf(a) + o.eps);
+    }
+    // (nk: Nadam's constants of this step — the touched-rows exchange only: apply_packed_kernel; a = m, b = v.  Adam: a = m,
+    // b = v, o.lr_t of this step — the touched-rows exchange only, the rows no list names take the sweep's G = 0 update)
     __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o, const NadamConsts &nk)
     {
         if (OPT == GLOVE_OPT_SGD) sgd(w, a, g, o);
         else if (OPT == GLOVE_OPT_ADAMAX) adamax(w, a, b, g, o);
         else if (OPT == GLOVE_OPT_ADADELTA) adadelta(w, a, b, g, o);
         else if (OPT == GLOVE_OPT_NADAM) nadam_elem(w, a, b, g, nk);
+        else if (OPT == GLOVE_OPT_RMSPROP) rmsprop(w, a, g, o);
+        else if (OPT == GLOVE_OPT_ADAM) adam_elem(w, a, b, g, o.lr_t, o.b1, o.b2, o.eps);
         else ftrl(w, a, b, g, o);
     }
     __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o) { one(w, a, b, g, o, NadamConsts{}); }
@@ -1433,40 +1444,93 @@ struct OptElem {
 // of them — and the rows are then moved two entries at a time, what each needs handed round by lane shuffles: one
 // round trip per pair of entries.
 // OPT: GLOVE_OPT_ADAGRAD, or one of the per-row Keras optimizers (OptElem: SGD, Adamax, Adadelta, Ftrl) — only touched rows move
-// under all of them, so the exchange is the same and the epilogue differs.  s2: the second slot of every variable where the
-// optimizer has one (scalars[2] for the global bias).
+// under all of them, so the exchange is the same and the epilogue differs.  The dense-decay ones (Nadam, Adam, RMSprop) move
+// every row's slots every step: decay_unmarked_kernel gives the rows no list names their G = 0 update first, and the listed
+// rows take the epilogue here.  s2: the second slot of every variable where the optimizer has one (scalars[2] for the global bias).
 struct SlotTwo { float *R, *C, *br, *bc; };
 
-// Nadam on the touched-rows exchange: m and v of every row NO rank touched decay (Keras' legacy sparse Nadam decays them over
-// the whole variable); the rows some rank touched — marked by count_packed_kernel — are apply_packed_kernel's, the next launch.
-template <int LPR, int NV>
-__global__ __launch_bounds__(kBlock) void nadam_decay_unmarked_kernel(DenseViews dv, SideBufs rs, SideBufs cs, SlotTwo s2, int d4,
-                                                                      float b1, float b2, int V)
+constexpr int kSweepRows = 2;       // table rows a sweep lane group keeps in flight (adam_fused_kernel, nadam_fused_kernel,
+                                    // decay_unmarked_kernel)
+
+// The dense-decay optimizers on the touched-rows exchange: every row NO rank touched (no count bits in its mark — count_packed_kernel
+// marked the lists' ids) takes the G = 0 update; the rows some rank touched are apply_packed_kernel's, the next launch.  Rows
+// [lo, hi) of the concatenation [row side | col side] are swept (the sides glove_hyper.sweep_sides selects).
+//   Nadam    m and v decay (Keras' legacy sparse Nadam decays them over the whole variable; the row stays)
+//   Adam     m and v decay and the row moves: W -= lr_t m / (sqrt(v) + eps), as adam_fused_kernel's sweep, bit for bit
+//   RMSprop  the rms slot decays (rho rms + (1 - rho) 0 = rho rms: dense_rmsprop_kernel's bits on a zero gradient)
+// A pure stream: kSweepRows rows in flight per lane group, everything requested before the mark is looked at (what a marked row
+// loaded is dropped), as adam_fused_kernel's sweep.
+template <int LPR, int NV, int OPT>
+__global__ __launch_bounds__(kBlock) void decay_unmarked_kernel(DenseViews dv, SideBufs rs, SideBufs cs, SlotTwo s2, int d4,
+                                                                float b1, float b2, float rho, float lr, float eps, double ln_beta1,
+                                                                double ln_beta2, const int64_t *__restrict__ step, int lo, int hi)
 {
     constexpr int GPB = kBlock / LPR;
+    constexpr bool kW = OPT == GLOVE_OPT_ADAM;                  // the row itself moves
+    constexpr bool kTwo = OPT != GLOVE_OPT_RMSPROP;             // m and v; RMSprop has its rms only
     const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    const int total = dv.V_row + V;
-    for (int v = blockIdx.x * GPB + grp; v < total; v += gridDim.x * GPB) {
-        if (dv.mark[v] & kMarkCountMask) continue;
-        const bool is_row = v < dv.V_row;
-        const int id = is_row ? v : v - dv.V_row;
-        const SideBufs &sb = is_row ? rs : cs;
-        float *S2 = is_row ? s2.R : s2.C, *S2b = is_row ? s2.br : s2.bc;
-        f4 M[NV], Vv[NV];
-        load_row<LPR, NV>(M, sb.S1, id, d4, lg);
-        load_row<LPR, NV>(Vv, S2, id, d4, lg);
+    const float lr_t = kW ? adam_lr_t(lr, ln_beta1, ln_beta2, *step) : 0.f;
+    const int stride = gridDim.x * GPB;
+    for (int v0 = lo + blockIdx.x * GPB + grp; v0 < hi; v0 += kSweepRows * stride) {
+        f4 Wv[kSweepRows][kW ? NV : 1], M[kSweepRows][NV], Vv[kSweepRows][kTwo ? NV : 1];
+        int mk[kSweepRows];
+        float bval[kSweepRows], Mb[kSweepRows], Vb[kSweepRows];
 #pragma unroll
-        for (int kk = 0; kk < NV; ++kk) { M[kk] = b1 * M[kk]; Vv[kk] = b2 * Vv[kk]; }
-        store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, M);
-        store_row<LPR, NV>(S2, (size_t)id, d4, lg, Vv);
-        if (lg == 0) { sb.S1b[id] = b1 * sb.S1b[id]; S2b[id] = b2 * S2b[id]; }
+        for (int r = 0; r < kSweepRows; ++r) {
+            const int v = v0 + r * stride;
+            const bool live = v < hi;
+            const bool is_row = v < dv.V_row;
+            const int id = live ? (is_row ? v : v - dv.V_row) : 0;
+            const SideBufs &sb = is_row ? rs : cs;
+            mk[r] = live ? dv.mark[v] & kMarkCountMask : 1;
+            if constexpr (kW) load_row<LPR, NV>(Wv[r], sb.W, id, d4, lg);
+            load_row<LPR, NV>(M[r], sb.S1, id, d4, lg);
+            if constexpr (kTwo) load_row<LPR, NV>(Vv[r], is_row ? s2.R : s2.C, id, d4, lg);
+            bval[r] = Mb[r] = Vb[r] = 0.f;
+            if (lg == 0) {
+                if constexpr (kW) bval[r] = sb.bias[id];
+                Mb[r] = sb.S1b[id];
+                if constexpr (kTwo) Vb[r] = (is_row ? s2.br : s2.bc)[id];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kSweepRows; ++r) {
+            if (mk[r]) continue;                                 // past the end, or the apply launch owns this row
+            const int v = v0 + r * stride;
+            const bool is_row = v < dv.V_row;
+            const int id = is_row ? v : v - dv.V_row;
+            const SideBufs &sb = is_row ? rs : cs;
+            if constexpr (OPT == GLOVE_OPT_ADAM) {
+                const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < NV; ++kk) adam_vec(Wv[r][kk], M[r][kk], Vv[r][kk], zero, lr_t, b1, b2, eps);
+                if (lg == 0) adam_elem(bval[r], Mb[r], Vb[r], 0.f, lr_t, b1, b2, eps);
+            } else if constexpr (OPT == GLOVE_OPT_NADAM) {
+#pragma unroll
+                for (int kk = 0; kk < NV; ++kk) { M[r][kk] = b1 * M[r][kk]; Vv[r][kk] = b2 * Vv[r][kk]; }
+                Mb[r] = b1 * Mb[r];
+                Vb[r] = b2 * Vb[r];
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < NV; ++kk) M[r][kk] = rho * M[r][kk];
+                Mb[r] = rho * Mb[r];
+            }
+            store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, M[r]);
+            if constexpr (kTwo) store_row<LPR, NV>(is_row ? s2.R : s2.C, (size_t)id, d4, lg, Vv[r]);
+            if constexpr (kW) store_row<LPR, NV>(sb.W, (size_t)id, d4, lg, Wv[r]);
+            if (lg == 0) {
+                sb.S1b[id] = Mb[r];
+                if constexpr (kTwo) (is_row ? s2.br : s2.bc)[id] = Vb[r];
+                if constexpr (kW) sb.bias[id] = bval[r];
+            }
+        }
     }
 }
 
 template <int LPR, int NV, int OPT>
 __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
     PackedLists pls, DenseViews dv, SideBufs rs, SideBufs cs, SlotTwo s2, int d4, StepConsts k, OptConsts o, double ln_beta1,
-    const int64_t *__restrict__ step, int first_tag, const float *__restrict__ tail_in, float *__restrict__ scalars,
+    double ln_beta2, const int64_t *__restrict__ step, int first_tag, const float *__restrict__ tail_in, float *__restrict__ scalars,
     float *__restrict__ loss_out, int do_scalars)
 {
     constexpr int GPB = kBlock / LPR;
@@ -1475,10 +1539,12 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
     const bool slots = kAdagrad || !(OPT == GLOVE_OPT_SGD && o.momentum == 0.f);     // (plain SGD keeps no slot)
     // t = global_step as the passes of this step left it (Adamax: lr_t = lr / (1 - beta1^t), as apply_sparse_opt_kernel)
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
-    // Nadam (the ranks' touched rows move; every other row's m and v have decayed in nadam_decay_unmarked_kernel, the launch before):
-    // the constants of step t = global_step as the passes left it; ln_beta1 carries ln beta2 here
+    // Adam (every row moves: the rows no list names took the G = 0 update in decay_unmarked_kernel, the launch before): lr_t of step t
+    if (OPT == GLOVE_OPT_ADAM) o.lr_t = adam_lr_t(o.lr, ln_beta1, ln_beta2, *step);
+    // Nadam (the ranks' touched rows move; every other row's m and v have decayed in decay_unmarked_kernel, the launch before):
+    // the constants of step t = global_step as the passes left it
     NadamConsts nk = {};
-    if (OPT == GLOVE_OPT_NADAM) nk = nadam_consts(o.lr, o.eps, o.b1, o.b2, ln_beta1, *step, scalars);
+    if (OPT == GLOVE_OPT_NADAM) nk = nadam_consts(o.lr, o.eps, o.b1, o.b2, ln_beta2, *step, scalars);
     const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
     const size_t stride4 = (size_t)d4 + 1;
     const PackedList &pl = pls.l[blockIdx.y];
@@ -1957,7 +2023,6 @@ __global__ __launch_bounds__(kBlock) void tagged_flush_kernel(float *__restrict_
 // (glove_plan.r_mark / c_mark) and leaves them alone.  scalars[3] says which copy is current between chains.  The global bias
 // travels through chain records like the tagged Adagrad step's ([0] bias, [1] m, [2] v as the step began).
 // ------------------------------------------------------------------------------------------
-constexpr int kSweepRows = 2;       // table rows a sweep lane group keeps in flight (adam_fused_kernel, nadam_fused_kernel)
 // ... in tagged_adam_kernel: four where the registers allow (d = 64: 10.8 -> 10.2 us per step; six spill: 14.2)
 constexpr int tagged_sweep_rows(int nv) { return nv <= 2 ? 4 : 2; }
 
@@ -3217,9 +3282,9 @@ int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_f
         // the other dense-decay optimizer of the Keras set: its whole rms slot decays every step, entries with a gradient move —
         // the sweep of glove_step_sparse_f32, here on a G_flat that holds the ranks' summed gradients (data-parallel step)
         if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
-        if (!(h->rho > 0.f && h->rho < 1.f) || sides != 3) return GLOVE_E_BADARG;
+        if (!(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
         hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, (hipStream_t)stream, segs, make_consts(t, h), h->rho,
-                           t->scalars, tail, loss_out, 1);
+                           t->scalars, tail, loss_out, (sides & 2) ? 1 : 0);
         return (int)hipGetLastError();
     }
     if (int rc = dense_common(t, h, G_flat, true, segs, tail, nbx, sides)) return rc;
@@ -3396,19 +3461,23 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
     if (int rc = packed_common(t, G_flat, mark, dv)) return rc;
     if (!h || !lists || n_lists < 1 || capacity_entries < 0) return GLOVE_E_BADARG;
     if (!t->R || !t->C || !t->br || !t->bc || !t->scalars || !t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc) return GLOVE_E_BADARG;
-    // glove_hyper.optimizer: Adagrad, or one of the per-row Keras optimizers (only touched rows move: the exchange is the same)
+    // glove_hyper.optimizer: Adagrad, one of the per-row Keras optimizers (only touched rows move: the exchange is the same), or
+    // a dense-decay one (Nadam, Adam, RMSprop: the sweep below moves the slots — Adam: the rows too — of every row no list names)
     const int opt = h->optimizer;
-    const bool two_slots = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL || opt == GLOVE_OPT_NADAM;
-    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && !two_slots) return GLOVE_E_BADARG;
+    const bool two_slots = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL || opt == GLOVE_OPT_NADAM ||
+                           opt == GLOVE_OPT_ADAM;
+    const bool decays = opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_RMSPROP;
+    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && !two_slots) return GLOVE_E_BADARG;
     if (two_slots && (!t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)) return GLOVE_E_BADARG;
-    if ((opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM) &&
+    if ((opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM) &&
         (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0) || !t->step)) return GLOVE_E_BADARG;
-    if (opt == GLOVE_OPT_NADAM && sides_of(h) != 3) return GLOVE_E_BADARG;                 // (m and v of BOTH tables decay every step)
-    if (opt == GLOVE_OPT_ADADELTA && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+    if ((opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_RMSPROP) && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+    if (h->sweep_sides < 0 || h->sweep_sides > 3) return GLOVE_E_BADARG;
     if (opt == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
     if (opt == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
     const OptConsts o = {h->learning_rate, h->epsilon, h->momentum, 0.f, (float)h->beta1, (float)h->beta2, h->nesterov ? 1 : 0, h->rho};
-    const double ln_b1 = opt == GLOVE_OPT_ADAMAX ? log((double)(float)h->beta1) : opt == GLOVE_OPT_NADAM ? log((double)(float)h->beta2) : 0.0;
+    const double ln_b1 = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADAM ? log((double)(float)h->beta1) : 0.0;
+    const double ln_b2 = opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM ? log((double)(float)h->beta2) : 0.0;
     const SlotTwo s2 = {t->s2_R, t->s2_C, t->s2_br, t->s2_bc};
     if (int rc = plain_table(t, stream)) return rc;
     const int d4 = t->d / 4;
@@ -3433,14 +3502,23 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         }
         tail = scratch;
     }
-    if (opt == GLOVE_OPT_NADAM) {
-        // the rows nobody touched: m and v decay (the marks are still whole: the apply launches below clear them as they go)
-        const int nbd = blocks_for((int64_t)v_row(t) + t->V, kBlock / shape.lpr);
-#define CALL(LPR, NV)                                                                                               \
-        hipLaunchKernelGGL((nadam_decay_unmarked_kernel<LPR, NV>), dim3(nbd), dim3(kBlock), 0, st, dv, rs, cs, s2, d4,   \
-                           (float)h->beta1, (float)h->beta2, (int)t->V)
-        GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+    if (decays) {
+        // the rows nobody touched on the swept sides take their G = 0 update (the marks are still whole: the apply launches below
+        // clear them as they go)
+        const int sweep = h->sweep_sides ? h->sweep_sides : sides_of(h);
+        const int lo = (sweep & 1) ? 0 : v_row(t), hi = (sweep & 2) ? v_row(t) + t->V : v_row(t);
+        const int nbd = blocks_for(((int64_t)(hi - lo) + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
+        const float b1 = (float)h->beta1, b2 = (float)h->beta2;
+#define LAUNCH_OPT(LPR, NV, OPT)                                                                                      \
+        hipLaunchKernelGGL((decay_unmarked_kernel<LPR, NV, OPT>), dim3(nbd), dim3(kBlock), 0, st, dv, rs, cs, s2, d4, b1, b2, \
+                           h->rho, h->learning_rate, h->epsilon, ln_b1, ln_b2, (const int64_t *)t->step, lo, hi)
+#define CALL(LPR, NV)                                                                                                 \
+        if (opt == GLOVE_OPT_ADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAM);                                               \
+        else if (opt == GLOVE_OPT_RMSPROP) LAUNCH_OPT(LPR, NV, GLOVE_OPT_RMSPROP);                                    \
+        else LAUNCH_OPT(LPR, NV, GLOVE_OPT_NADAM)
+        if (hi > lo) GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
+#undef LAUNCH_OPT
     }
     for (int32_t first = 0; first < n_lists; first += 8) {
         PackedLists pls;
@@ -3455,13 +3533,15 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         const int scal = first == 0 ? do_scalars : 0;
 #define LAUNCH_OPT(LPR, NV, OPT)                                                                                     \
         hipLaunchKernelGGL((apply_packed_kernel<LPR, NV, OPT>), dim3(nbx, pls.n), dim3(kBlock), 0, st, pls, dv, rs, cs, s2, \
-                           d4, k, o, ln_b1, (const int64_t *)t->step, (int)first, tail, t->scalars, loss_out, scal)
+                           d4, k, o, ln_b1, ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars, loss_out, scal)
 #define CALL(LPR, NV)                                                                                               \
         if (opt == GLOVE_OPT_ADAGRAD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAGRAD);                                       \
         else if (opt == GLOVE_OPT_SGD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_SGD);                                          \
         else if (opt == GLOVE_OPT_ADAMAX) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAMAX);                                    \
         else if (opt == GLOVE_OPT_ADADELTA) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADADELTA);                                \
         else if (opt == GLOVE_OPT_NADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_NADAM);                                      \
+        else if (opt == GLOVE_OPT_ADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAM);                                        \
+        else if (opt == GLOVE_OPT_RMSPROP) LAUNCH_OPT(LPR, NV, GLOVE_OPT_RMSPROP);                                  \
         else LAUNCH_OPT(LPR, NV, GLOVE_OPT_FTRL)
         GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef LAUNCH_OPT
@@ -3706,9 +3786,11 @@ int glove_steps_adagrad_f32(const glove_plan *const *plans, int32_t n, const glo
     return 0;
 }
 
-// passes (marking the batch's ids) + adam_fused_kernel: see the kernel's header
+// passes (marking the batch's ids) + adam_fused_kernel: see the kernel's header.  which = 1: the row side alone (the row pass,
+// the row ids' apply, the sweep over R's rows; no scalar work — glove_rowside_step_f32, whose G_flat IS the V_row marks), 3: both
+// sides (the marks in G_flat's bias segments)
 static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                           float *G_flat, float *loss_out, void *stream, bool nadam = false)
+                           float *G_flat, float *loss_out, void *stream, bool nadam = false, int which = 3)
 {
     if (int rc = check_common(p, t, h, ws)) return rc;
     if (!G_flat || !t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc || !t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)
@@ -3716,17 +3798,18 @@ static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glo
     if (!(h->beta1 > 0.0 && h->beta1 < 1.0 && h->beta2 > 0.0 && h->beta2 < 1.0)) return GLOVE_E_BADARG;
     const int32_t Vr = v_row(t);
     const GradLayout L = grad_layout(Vr, t->V, t->d);
-    float *mark_rows = G_flat + L.G_br, *mark_cols = G_flat + L.G_bc;
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3, mark_rows, mark_cols)) return rc;
+    float *mark_rows = which & 2 ? G_flat + L.G_br : G_flat, *mark_cols = which & 2 ? G_flat + L.G_bc : nullptr;
+    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, which, mark_rows, mark_cols)) return rc;
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
     const int d4 = t->d / 4;
     const RowShape shape = pick_row_shape(d4);
     IdWork wk = id_work(p);
-    wk.sides = 3;
+    wk.sides = which;
+    const int32_t Vc = which & 2 ? t->V : 0;         // col rows the sweep covers (behind R's rows)
     // a multiple of 8 workgroups in front: workgroups b and b + 8 share an XCD, so every step's sweep then finds
     // the rows it wrote last step in the same L2s, whatever the batch's id count (5.3 vs 11 us per launch)
     const int apply_blocks = (wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1 + 7) & ~7;
-    const int nb = apply_blocks + blocks_for(((int64_t)Vr + t->V + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
+    const int nb = apply_blocks + blocks_for(((int64_t)Vr + Vc + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
     const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
     const StepConsts k = make_consts(t, h);
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
@@ -3735,15 +3818,17 @@ static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glo
     if (nadam)                                                                                                 \
         hipLaunchKernelGGL((nadam_fused_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
                            t->s2_br, t->s2_bc, d4, k, (float)h->beta1, (float)h->beta2, log((double)(float)h->beta2), \
-                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)t->V, \
+                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc,   \
                            apply_blocks, loss_out);                                                            \
     else                                                                                                       \
         hipLaunchKernelGGL((adam_fused_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
                            t->s2_br, t->s2_bc, d4, k, (float)h->beta1, (float)h->beta2, log((double)(float)h->beta1), log((double)(float)h->beta2),  \
-                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)t->V, \
+                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc,   \
                            apply_blocks, loss_out)
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
+    if (which == 1)         // the row pass's loss partials, folded: any later reader finds them whatever grid it assumes
+        hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, st, w.blockpart, nb_row);
     return (int)hipGetLastError();
 }
 
@@ -3889,6 +3974,66 @@ int glove_step_sparse_f32(const glove_plan *p, const glove_tables *t, const glov
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
 #undef LAUNCH_OPT
+    return (int)hipGetLastError();
+}
+
+int glove_rowside_step_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
+                           float *G_flat, void *stream)
+{
+    if (!p || !t || !h || sides_of(h) != 1) return GLOVE_E_BADARG;          // hyper.sides = 1: this is the row side's step
+    if (h->optimizer == GLOVE_OPT_ADAGRAD) return glove_rowside_step_adagrad_f32(p, t, h, ws, ws_bytes, stream);
+    if (int rc = plain_table(t, stream)) return rc;
+    if (int rc = check_common(p, t, h, ws)) return rc;
+    if (!t->s1_R || !t->s1_br) return GLOVE_E_BADARG;
+    const int opt = h->optimizer;
+    if (opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_NADAM)
+        // the row pass marks the batch's row ids; one kernel applies them and gives every other row of the shard its G = 0 update
+        return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, nullptr, stream, opt == GLOVE_OPT_NADAM, 1);
+    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
+    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int d4 = t->d / 4;
+    const RowShape shape = pick_row_shape(d4);
+    const StepConsts k = make_consts(t, h);
+    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
+    if (opt == GLOVE_OPT_RMSPROP) {
+        // the row half of glove_step_sparse_f32's RMSprop: the summed row gradients into G_flat, the sweep over R's rms slot
+        if (!G_flat || !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
+        if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
+        DenseSegs segs; float *tail; int nbx, sides;
+        if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
+        hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, h->rho, t->scalars, tail, nullptr, 0);
+    } else {
+        // the per-row optimizers: the row pass, then their epilogue on the row ids (apply_sparse_opt_kernel, sides 1: no scalar work)
+        const bool two_slots = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL;
+        if (opt != GLOVE_OPT_SGD && !two_slots) return GLOVE_E_BADARG;
+        if (two_slots && (!t->s2_R || !t->s2_br)) return GLOVE_E_BADARG;
+        if (opt == GLOVE_OPT_ADAMAX && (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0))) return GLOVE_E_BADARG;
+        if (opt == GLOVE_OPT_ADADELTA && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+        if (opt == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
+        if (opt == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
+        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
+        IdWork wk = id_work(p);
+        wk.sides = 1;
+        const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
+        const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
+        const OptConsts o = {h->learning_rate, h->epsilon, h->momentum, 0.f, (float)h->beta1, (float)h->beta2, h->nesterov ? 1 : 0, h->rho};
+        const double ln_b1 = opt == GLOVE_OPT_ADAMAX ? log((double)(float)h->beta1) : 0.0;
+#define LAUNCH_OPT(LPR, NV, OPT)                                                                                           \
+        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, OPT>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
+                           t->s2_br, t->s2_bc, d4, k, o, ln_b1, (const int64_t *)t->step, t->scalars, (const float *)w.blockpart, nb_row, nullptr)
+#define CALL(LPR, NV)                                                                                                       \
+        if (opt == GLOVE_OPT_SGD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_SGD);                                                      \
+        else if (opt == GLOVE_OPT_ADAMAX) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAMAX);                                           \
+        else if (opt == GLOVE_OPT_ADADELTA) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADADELTA);                                       \
+        else LAUNCH_OPT(LPR, NV, GLOVE_OPT_FTRL)
+        GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+#undef CALL
+#undef LAUNCH_OPT
+    }
+    // the row pass's loss partials, folded: glove_loss_partials_f32 / the col side's dense gradient find them whatever grid they assume
+    hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, st, w.blockpart, nb_row);
     return (int)hipGetLastError();
 }
 

@@ -46,7 +46,7 @@ FLAGS = (
     Flag("embedding-size", int, config.EMBEDDING_SIZE, "columns of the row and column embedding tables"),
     Flag("l2-reg", float, config.L2_REG, "activity-L2 coefficient"),
     Flag("neg-factor", float, config.NEG_FACTOR, "weight of the negative head's loss (logistic heads)"),
-    Flag("optimizer", str, config.OPTIMIZER, "Keras optimizer name: Adagrad or Adam"),
+    Flag("optimizer", str, config.OPTIMIZER, "Keras optimizer name: Adagrad, Adam, SGD, RMSprop, Adamax, Nadam, Adadelta or Ftrl"),
     Flag("learning-rate", float, config.LEARNING_RATE, "optimizer step size"),
     Flag("batch-size", int, config.BATCH_SIZE, "nonzeros per step and rank"),
     Flag("train-steps", int, config.TRAIN_STEPS, "absolute global_step to stop at"),
@@ -73,7 +73,7 @@ FLAGS = (
                                            "one GPU always does"),
     Flag("row-sharded", None, False, "multi-GPU: shard the row table (and its slots) by row id % ranks and route every "
                                      "nonzero to the rank that owns its row, instead of replicating all tables "
-                                     "(BASELINE config 5; Adagrad only)"),
+                                     "(BASELINE config 5; any of the eight optimizer names)"),
     Flag("shard-cols", None, False, "with --row-sharded: shard the col table as well (rows and cols on id % ranks; a step fetches "
                                     "the col rows its batch touches from their owners and returns their gradients: two "
                                     "all-to-alls whose size follows the batch, not the vocabulary); --epoch-shuffle full only"),

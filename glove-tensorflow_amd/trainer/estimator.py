@@ -77,8 +77,6 @@ class Estimator:
         if params.get("shard_cols") and not params.get("row_sharded"):
             raise ValueError("--shard-cols goes with --row-sharded")
         if self.row_sharded:
-            if self.optimizer_name != "Adagrad":
-                raise ValueError("--row-sharded is implemented for Adagrad (Keras' Adam has no sparse form)")
             # keep this rank's rows (u % world == rank) of the row side; the col side stays replicated, or is cut the same way
             from trainer.hip_api import DeviceTables
             from trainer.stepper import owned_rows

@@ -18,7 +18,7 @@ logger = logging.getLogger(__name__)
 PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
 
-GLOVE_ABI_VERSION = 13
+GLOVE_ABI_VERSION = 14
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7}      # glove_hyper.optimizer (GLOVE_OPT_*)
 STEP_AUTO, STEP_TWO_LAUNCH, STEP_FUSED_ONE_PASS, STEP_FUSED_THREE_LAUNCH, STEP_FUSED_TWIN, STEP_TAGGED = 0, 1, 2, 3, 4, 5   # glove_hyper.step_form (2: tests / comparisons only)
@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "glove_count_packed_f32",
     "glove_masters_workspace_bytes", "glove_masters_build", "glove_epoch_deal_workspace_bytes", "glove_epoch_deal",
     "glove_plan_sorted_workspace_bytes", "glove_plan_chunk_bound", "glove_plan_build_sorted", "glove_step_sparse_f32",
+    "glove_rowside_step_f32",
 )
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -73,7 +74,8 @@ class GloveHyper(C.Structure):
                 ("l2_reg", C.c_float), ("reg_mult", C.c_float), ("learning_rate", C.c_float),
                 ("epsilon", C.c_float), ("inv_batch", C.c_float), ("sides", C.c_int32),
                 ("head", C.c_int32), ("neg_factor", C.c_float), ("step_form", C.c_int32),
-                ("optimizer", C.c_int32), ("momentum", C.c_float), ("nesterov", C.c_int32), ("rho", C.c_float)]
+                ("optimizer", C.c_int32), ("momentum", C.c_float), ("nesterov", C.c_int32), ("rho", C.c_float),
+                ("sweep_sides", C.c_int32)]
 
 
 class GlovePlan(C.Structure):
@@ -155,6 +157,7 @@ def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CD
         "glove_gather_rows_f32": (C.c_int, [vp, vp, vp, i32, i32, vp, vp, vp]),
         "glove_canonicalize_f32": (C.c_int, [P(GloveTables), vp]),
         "glove_rowside_step_adagrad_f32": (C.c_int, [P(GlovePlan), P(GloveTables), P(GloveHyper), vp, sz, vp]),
+        "glove_rowside_step_f32": (C.c_int, [P(GlovePlan), P(GloveTables), P(GloveHyper), vp, sz, vp, vp]),
         "glove_eval_f32": (C.c_int, [vp, vp, vp, vp, i64, P(GloveTables), vp, vp]),
         "glove_eval_logistic_f32": (C.c_int, [vp, vp, vp, vp, i64, P(GloveTables), vp, vp]),
         "glove_topk_workspace_bytes": (sz, [i32, i32, i32]),
@@ -760,11 +763,12 @@ class PlanBlock:
 
 def make_hyper(l2_reg=0.01, reg_mult=2.0, learning_rate=0.001, epsilon=1e-7, beta1=0.9, beta2=0.999,
                batch_size=None, inv_batch=None, sides=0, head=HEAD_REGRESSION, neg_factor=1.0,
-               step_form=STEP_AUTO, optimizer="Adagrad", momentum=0.0, nesterov=False, rho=None) -> GloveHyper:
+               step_form=STEP_AUTO, optimizer="Adagrad", momentum=0.0, nesterov=False, rho=None, sweep_sides=0) -> GloveHyper:
     """`sides`: 0/3 both sides, 1 row side only, 2 col side only; `head`: HEAD_REGRESSION (GloVe) or
-    HEAD_LOGISTIC (pos/neg logistic matrix factorisation, with `neg_factor`) — see glove_hyper in the header."""
+    HEAD_LOGISTIC (pos/neg logistic matrix factorisation, with `neg_factor`); `sweep_sides`: the sides whose unlisted rows
+    the touched-rows apply sweeps under Adam / RMSprop / Nadam (0 = `sides`) — see glove_hyper in the header."""
     h = GloveHyper()
-    h.sides, h.head, h.neg_factor, h.step_form = sides, head, neg_factor, step_form
+    h.sides, h.head, h.neg_factor, h.step_form, h.sweep_sides = sides, head, neg_factor, step_form, sweep_sides
     h.optimizer = OPTIMIZER_CODES[optimizer] if isinstance(optimizer, str) else int(optimizer)     # read by glove_step_sparse_f32 only
     if rho is None:                     # the optimizer's own Keras default
         rho = 0.95 if h.optimizer == OPTIMIZER_CODES["Adadelta"] else 0.9
@@ -947,6 +951,15 @@ class GloveHip:
         ws = self.step_workspace(plan, tables.d) if ws is None else ws
         _check(self.lib.glove_rowside_step_adagrad_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
                                                        _ptr(ws), ws.numel(), _stream()), "glove_rowside_step_adagrad_f32")
+
+    def rowside_step_opt(self, plan, tables, hyper, G_flat=None, ws=None):
+        """The row side of a step under the optimizer `tables.optimizer` names (hyper.sides = 1; glove_rowside_step_f32).
+        G_flat: a dense gradient buffer of these tables (all zero between calls) — Adam, RMSprop and Nadam mark or sum the
+        row ids in it."""
+        ws = self.step_workspace(plan, tables.d) if ws is None else ws
+        hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]
+        _check(self.lib.glove_rowside_step_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper), _ptr(ws),
+                                               ws.numel(), _ptr(G_flat), _stream()), "glove_rowside_step_f32")
 
     def apply_adagrad(self, plan, tables, hyper, loss_out=None, ws=None):
         ws = self.step_workspace(plan, tables.d) if ws is None else ws

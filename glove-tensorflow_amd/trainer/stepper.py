@@ -34,6 +34,7 @@ class HipBackend:
         self.row_floats = None      # floats per table row, once the tables exist: lets resident plans carry what the fused step needs
         self.shard_rows = 0         # rows of this rank's row-table shard when the row ids handed in are shard-local (else 0)
         self.exchange = False       # the plans feed a multi-rank step: its packing passes read chunk records, not run words
+        self._row_G = {}            # (optimizer, V_row, d) -> the row-side step's scratch when the caller lends none
 
     def build_plan(self, row, col, w, y, V, chunk_cap):
         return self.hip.build_plan(row.contiguous(), col.contiguous(), w.contiguous(), y.contiguous(), V,
@@ -83,8 +84,20 @@ class HipBackend:
     def colpass(self, plan, tables, hyper):
         self.hip.colpass(plan, tables, hyper)
 
-    def rowside_step(self, plan, tables, hyper):
-        self.hip.rowside_step(plan, tables, hyper)
+    def rowside_step(self, plan, tables, hyper, G=None):
+        """G (the other Keras names): a dense gradient buffer of `tables` whose row half is zero between steps — the step's
+        scratch (glove_rowside_step_f32: Adam and Nadam mark the row ids in its first V_row floats, RMSprop sums the row
+        gradients into its row half, all zero again afterwards).  None: the backend keeps the least scratch that serves."""
+        if tables.optimizer == "Adagrad":
+            self.hip.rowside_step(plan, tables, hyper)
+            return
+        if G is None and tables.optimizer in ("Adam", "RMSprop", "Nadam"):
+            key = (tables.optimizer, tables.V_row, tables.d)
+            G = self._row_G.get(key)
+            if G is None:
+                n = self.hip.grad_layout(tables)["G_C"] if tables.optimizer == "RMSprop" else tables.V_row
+                G = self._row_G[key] = torch.zeros(n, dtype=torch.float32, device=tables.device)
+        self.hip.rowside_step_opt(plan, tables, hyper, G)
 
     def dense_grad(self, plan, tables, hyper, G):
         self.hip.dense_grad(plan, tables, hyper, G)
@@ -152,18 +165,25 @@ class HipBackend:
 
     def owner_apply(self, tables, state, recv, ids, counts, hyper, tail, loss_out):
         """The owner's half of the col side: `recv` holds, rank after rank, the summed gradient rows the ranks computed
-        for this rank's col rows `ids` (owner-local indices); they are added in rank order and Adagrad is applied."""
+        for this rank's col rows `ids` (owner-local indices); they are added in rank order and the optimizer is applied.
+        Under Adam, RMSprop and Nadam every other row of the shard takes its G = 0 update (the sweep of side 0 only)."""
         from trainer.hip_api import TablesView
         if "view" not in state:
             f32 = dict(dtype=torch.float32, device=tables.device)
             dummy, dummy_b = torch.zeros(4, tables.d, **f32), torch.zeros(4, **f32)
-            # the col shard sits on the ROW side of this view (entries of side 0); its col side is a 4-row dummy
+            # the col shard sits on the ROW side of this view (entries of side 0); its col side is a 4-row dummy, which the
+            # apply never sweeps (sweep_sides = 1) while the scalar work still goes with sides = 3
+            slots2 = dict(s2_R=tables.s2["C"], s2_br=tables.s2["bc"], s2_C=dummy, s2_bc=dummy_b) if "C" in tables.s2 else {}
             view = TablesView(tables, R=tables.C, br=tables.bc, s1_R=tables.s1["C"], s1_br=tables.s1["bc"],
                               C=dummy, bc=dummy_b, s1_C=dummy, s1_bc=dummy_b, V=4, V_row=tables.C.shape[0],
-                              keep=(dummy, dummy_b))
+                              keep=(dummy, dummy_b), **slots2)
             state.update(view=view, G=self.hip.dense_grad_buffer(view),
                          mark=torch.zeros(view.V_row + view.V, dtype=torch.int32, device=tables.device))
-        view, G, mark = state["view"], state["G"], state["mark"]
+        if state.get("hyper_src") is not hyper:
+            h = type(hyper).from_buffer_copy(hyper)
+            h.sweep_sides = 1
+            state.update(hyper=h, hyper_src=hyper)
+        view, G, mark, hyper = state["view"], state["G"], state["mark"], state["hyper"]
         lists, off = [], 0
         for n in counts:                      # a rank whose batch touches none of this owner's rows sends nothing
             if n:
@@ -467,13 +487,46 @@ def route_by_row_owner(coo: dict, world: int, rank: int, dist) -> dict:
     return out
 
 
+KERAS_OPTIMIZERS = ("Adagrad", "SGD", "RMSprop", "Adamax", "Adam", "Adadelta", "Ftrl", "Nadam")
+
+
+def plain_step_phases(backend, tables, hyper, loss_out, G):
+    """The single-GPU step of `tables.optimizer` as Stepper runs it on one rank, as [(name, fn(plan))]: a sharded form alone in
+    the world takes exactly these launches.  G: the dense gradient buffer of Adam, RMSprop and Nadam (plain_step_buffer)."""
+    b, t, h = backend, tables, hyper
+    if t.optimizer == "Adam":
+        return [("passes", lambda p: b.passes(p, t, h)), ("dense_grad", lambda p: b.dense_grad(p, t, h, G)),
+                ("dense_apply", lambda p: b.apply_dense(t, h, G, loss_out))]
+    if t.optimizer in ("RMSprop", "Nadam") and hasattr(b, "hip"):
+        return [("step", lambda p: b.hip.step_sparse(p, t, h, G, loss_out))]
+    return [("step", lambda p: b.step_sparse_adagrad(p, t, h, loss_out))]
+
+
+def plain_step_buffer(backend, tables):
+    return backend.dense_grad_buffer(tables) if tables.optimizer in ("Adam", "RMSprop", "Nadam") else None
+
+
+def sharded_exchange(tables, exchange: str, multi: bool) -> str:
+    """The col-side exchange a row-sharded form takes for `tables.optimizer`: the per-row optimizers and Nadam (only
+    touched rows move) need the lists — the union of the ranks' ids —, Adagrad, Adam and RMSprop take either."""
+    if tables.optimizer not in KERAS_OPTIMIZERS:
+        raise ValueError("the sharded forms take the eight Keras names (%s), got %s" % (", ".join(KERAS_OPTIMIZERS), tables.optimizer))
+    if exchange not in ("auto", "dense", "rows"):
+        raise ValueError("exchange must be auto, dense or rows")
+    if multi and tables.optimizer in Stepper.ROWS_ONLY:
+        if exchange == "dense":
+            raise ValueError("%s runs on the touched-rows exchange (its dense form would need the ranks' id marks)" % tables.optimizer)
+        return "rows"
+    return exchange
+
+
 class RowShardedStepper(GraphedSteps):
-    """Model-parallel form of BASELINE config 5.  The row table R / br (and their Adagrad accumulators) are
+    """Model-parallel form of BASELINE config 5.  The row table R / br (and their optimizer slots) are
     sharded by row id % world; the col table, the global bias and their slots are replicated.  Every rank
     steps on nonzeros whose rows it owns (see route_by_row_owner), so
 
-      * the row side is completely local: rowpass / colpass, then a sparse Adagrad apply restricted to the
-        row side (hyper.sides = 1) — no communication;
+      * the row side is completely local: rowpass / colpass, then the optimizer's apply restricted to the
+        row side (hyper.sides = 1; Adam, RMSprop, Nadam: every row of the shard moves) — no communication;
       * the col side is data parallel: either the rank's summed col gradients (hyper.sides = 2) go into the
         contiguous [G_C | G_bc | tail] half of the flat buffer, ONE all-reduce sums it over the ranks and every rank
         applies the identical dense update of C, bc and the global bias (`exchange="dense"`); or the ranks all-gather
@@ -481,16 +534,15 @@ class RowShardedStepper(GraphedSteps):
         instead of V; "auto" picks it in `prepare(plans)` when the lists are the shorter payload).
 
     With inv_batch = 1 / (world * B) the result equals a single-GPU step on the union of the ranks'
-    batches (tests/test_dp_gloo.py).  On one rank nothing is exchanged and the step is the plain sparse one."""
+    batches (tests/test_dp_gloo.py).  On one rank nothing is exchanged and the step is the plain single-GPU one.
+    All eight Keras names: the per-row ones and Nadam take the lists' exchange, Adagrad, Adam and RMSprop either."""
 
     def __init__(self, backend, tables, hyper_kwargs: dict, batch_size: int, world: int, dist, exchange="auto",
                  collectives=False):
-        if tables.optimizer != "Adagrad":
-            raise ValueError("the row-sharded step is implemented for Adagrad (Keras Adam has no sparse form)")
-        if exchange not in ("auto", "dense", "rows"):
-            raise ValueError("exchange must be auto, dense or rows")
         self.backend, self.tables, self.world, self.dist = backend, tables, int(world), dist
         self._multi = self.world > 1 or bool(collectives)      # collectives: the transport even with one rank (tests)
+        exchange = sharded_exchange(tables, exchange, self._multi)
+        hyper_kwargs = dict(hyper_kwargs, optimizer=tables.optimizer)
         if self._multi and hasattr(backend, "exchange"):
             backend.exchange = True         # plans built from here on keep chunk records (the packing passes read them)
         gb = batch_size * self.world
@@ -500,9 +552,9 @@ class RowShardedStepper(GraphedSteps):
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=tables.device)
         self.tail = torch.zeros(4, dtype=getattr(backend, "tail_dtype", torch.float32), device=tables.device)   # loss partials over the ranks
         self._gather = SideCollective(tables.device)        # the lists' all-gather while it is in flight
-        self.G = backend.dense_grad_buffer(tables) if self._multi else None
+        self.G = backend.dense_grad_buffer(tables) if self._multi else plain_step_buffer(backend, tables)
         self.exchange, self.rows, self.bufs = exchange, False, None
-        self.payload_floats = int(backend.col_half(tables, self.G).numel()) if self.G is not None else 0
+        self.payload_floats = int(backend.col_half(tables, self.G).numel()) if self._multi else 0
 
     def prepare(self, plans=None, batch_size=None):
         """Agree (collectively) on the col-side exchange: from the col id counts of all resident plans (static stream) or,
@@ -522,13 +574,17 @@ class RowShardedStepper(GraphedSteps):
     def phases(self):
         b, t = self.backend, self.tables
         if not self._multi:
-            return [("step", lambda p: b.step_sparse_adagrad(p, t, self.hyper, self.loss_out))]
+            return plain_step_phases(b, t, self.hyper, self.loss_out, self.G)
         # the col pass first (it gathers the old rows of R), then the whole row side, applied in place by its pass where a
         # lane group holds an id completely: R, br are local, nothing else reads them in this step
         if self.rows:       # the col pass already writes the list entries of the col ids it sums completely
             ph = [("colpass", lambda p: b.passes_packing(p, t, self.hyper_cols, self.bufs["send"]))]
         else:
             ph = [("colpass", lambda p: b.colpass(p, t, self.hyper_cols))]
+        if t.optimizer == "Adagrad":
+            rowside = lambda p: b.rowside_step(p, t, self.hyper_rows)
+        else:   # the row half of self.G is zero between steps (the col exchange uses the col half): the row side's scratch
+            rowside = lambda p: b.rowside_step(p, t, self.hyper_rows, self.G)
         if self.rows:
             # the lists travel while the row side runs: the all-gather is started (it waits for what this stream has
             # enqueued — the list is complete) and awaited after the row side; the loss partials, which the row pass
@@ -543,12 +599,12 @@ class RowShardedStepper(GraphedSteps):
 
             ph += [("pack_grad_cols", lambda p: b.pack_rest(p, t, self.hyper_cols, self.bufs["send"])),      # reads C: before its update
                    ("all_gather", gather),
-                   ("rowside_step", lambda p: b.rowside_step(p, t, self.hyper_rows)),
+                   ("rowside_step", rowside),
                    ("loss_tail", loss_tail),
                    ("combine_apply_cols", lambda p: b.apply_gathered(self.bufs, self.world, t, self.hyper_cols, self.G,
                                                                        self.loss_out, self.tail))]
         else:
-            ph.append(("rowside_step", lambda p: b.rowside_step(p, t, self.hyper_rows)))
+            ph.append(("rowside_step", rowside))
             ph += [("dense_grad_cols", lambda p: b.dense_grad(p, t, self.hyper_cols, self.G)),   # reads C (activity-L2 term): before its update
                    ("all_reduce", lambda p: self.dist.all_reduce(b.col_half(t, self.G))),
                    ("dense_adagrad_cols", lambda p: b.apply_dense(t, self.hyper_cols, self.G, self.loss_out))]
@@ -592,8 +648,8 @@ class ShardedStepper(GraphedSteps):
         the duplicates of ALL ranks' slices before it squares, a9 / a10, so its gradient waits for the other ranks' lists
         like everybody else's.)  `exercise_exchange`: run the full serve / fetch / push / owner-apply sequence on one rank
         all the same (tests: every collective of the form really goes through the transport on a one-GPU box)."""
-        if tables.optimizer != "Adagrad":
-            raise ValueError("the sharded step is implemented for Adagrad (Keras Adam has no sparse form)")
+        sharded_exchange(tables, "rows", False)            # (the eight Keras names; the col side always travels as lists)
+        hyper_kwargs = dict(hyper_kwargs, optimizer=tables.optimizer)
         self.backend, self.tables, self.world, self.rank, self.dist = backend, tables, int(world), int(rank), dist
         self._multi = self.world > 1 or bool(collectives)      # collectives: the transport even with one rank (tests)
         if self._multi and hasattr(backend, "exchange"):
@@ -602,7 +658,7 @@ class ShardedStepper(GraphedSteps):
         self.col_per = 0        # > 0: the col ids handed in are numbered owner-major, ceil(V / world) per owner (the runner sets it from its stream)
         if hasattr(backend, "exchange"):
             backend.exchange = not self.local_only      # (alone in the world the step is the plain one: run words will do)
-        if self.local_only and hasattr(tables, "maybe_enable_twin"):
+        if self.local_only and tables.optimizer == "Adagrad" and hasattr(tables, "maybe_enable_twin"):
             tables.maybe_enable_twin()
         gb = batch_size * self.world
         self.hyper = backend.make_hyper(batch_size=gb, **hyper_kwargs)
@@ -614,6 +670,7 @@ class ShardedStepper(GraphedSteps):
         self._push = SideCollective(tables.device)          # the col gradients' all-to-all while it is in flight
         self._prep_pg = None                                # the communicator of the prepare's collectives (prepare_group)
         self._spare = {}                                    # staging plans of dropped batches, by (B, id bound, chunk cap)
+        self.G = plain_step_buffer(backend, tables) if self.local_only else None     # (alone in the world: the plain step's)
         if hasattr(backend, "shard_rows"):
             backend.shard_rows = tables.V_row       # local row ids: anything outside the shard counts as id 0, like a bad col id
 
@@ -801,7 +858,7 @@ class ShardedStepper(GraphedSteps):
         b, t, dist, W = self.backend, self.tables, self.dist, self.world
         if self.local_only:
             bt = self.batches
-            ph = [("step", lambda i: b.step_sparse_adagrad(bt[i]["plan"], t, self.hyper, self.loss_out))]
+            ph = [(name, lambda i, fn=fn: fn(bt[i]["plan"])) for name, fn in plain_step_phases(b, t, self.hyper, self.loss_out, self.G)]
             if self._multi:         # `collectives`: the loss scalars still travel through the transport (a sum over one rank)
                 ph.append(("loss_tail", lambda i: dist.all_reduce(self.loss_out)))
             return ph

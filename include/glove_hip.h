@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GLOVE_ABI_VERSION 13   /* 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
+#define GLOVE_ABI_VERSION 14   /* 14: glove_hyper.sweep_sides; glove_apply_packed_adagrad_f32 takes GLOVE_OPT_ADAM and GLOVE_OPT_RMSPROP and applies the dense-decay optimizers (Adam, RMSprop, Nadam) to one side; glove_dense_adam_f32 applies RMSprop to one side; glove_rowside_step_f32 (the row side of a step under any of the eight optimizers): the sharded multi-GPU forms run every Keras optimizer; 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
 
 #define GLOVE_E_BADARG   (-1)   /* null pointer / non-positive size / d % 4 != 0 */
 #define GLOVE_E_WORKSPACE (-2)  /* workspace or plan storage too small */
@@ -152,6 +152,12 @@ typedef struct glove_hyper {
     float momentum;             /* SGD, Keras default 0 */
     int32_t nesterov;           /* SGD, Keras default 0 */
     float rho;                  /* RMSprop (Keras default 0.9), Adadelta (0.95) */
+    /* which sides' rows NO list names glove_apply_packed_adagrad_f32 sweeps under the dense-decay optimizers (Adam, RMSprop,
+     * Nadam: every row's slots move every step): 0 = the sides `sides` selects, otherwise 1 = row side, 2 = col side, 3 = both.
+     * `sides` alone keeps deciding the scalar duty (global bias, loss_out: with the col side).  A caller that stands a table
+     * shard on the row side of a view whose col side is a stand-in (an owner's apply of a sharded col table) sets sides = 3
+     * and sweep_sides = 1: the stand-in is never touched, the scalar work still happens. */
+    int32_t sweep_sides;
 } glove_hyper;
 
 #define GLOVE_OPT_ADAGRAD 0
@@ -353,7 +359,8 @@ int glove_dense_grad_f32(const glove_plan *plan, const glove_tables *t, const gl
 int glove_dense_adagrad_f32(const glove_tables *t, const glove_hyper *h, float *G_flat,
                             float *loss_out, void *stream);
 /* (Keras-legacy Adam; with glove_hyper.optimizer = GLOVE_OPT_RMSPROP the legacy RMSprop sweep instead: the whole rms slot decays,
- * entries with a non-zero summed gradient move) */
+ * entries with a non-zero summed gradient move.  Both sweep the sides hyper.sides selects — the col half alone under a sharded
+ * row table — and do the scalar work with the col side.) */
 int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_flat,
                          float *loss_out, void *stream);
 
@@ -410,8 +417,11 @@ int glove_count_packed_f32(const glove_packed_list *lists, int32_t n_lists, cons
 int glove_combine_packed_f32(const glove_packed_list *list, int32_t tag, const glove_tables *t, float *G_flat,
                              int32_t *mark, int64_t capacity_entries, void *stream);
 /* The optimizer glove_hyper.optimizer names — Adagrad, or one of the per-row Keras optimizers (GLOVE_OPT_SGD, _ADAMAX, _ADADELTA,
- * _FTRL: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*; and
- * GLOVE_OPT_NADAM, both sides in one call: the rows NO list names have their m and v decayed first, the named ones move) — on
+ * _FTRL: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*), or one
+ * of the dense-decay ones, whose slots move on every row every step: first the rows NO list names on the sides
+ * glove_hyper.sweep_sides selects take their G = 0 update (GLOVE_OPT_NADAM: m and v decay; GLOVE_OPT_ADAM: m and v decay and
+ * the row moves, lr_t of t = global_step; GLOVE_OPT_RMSPROP: the rms slot decays) — which needs the lists counted into `mark`
+ * first (glove_count_packed_f32) — then the named ones move — on
  * every id the lists touched (lists[i] was combined with tag i): each id is applied from the list that
  * touched it first, its mark is cleared.  tail: device float[4] {sum_e, sum w diff^2, sum |r|^2+|c|^2, sum b^2}
  * already summed over the ranks, or NULL = summed here over the lists' headers in list order.  With the col side
@@ -435,6 +445,18 @@ int glove_step_adagrad_f32(const glove_plan *plan, const glove_tables *t, const 
  * BEFORE this call.  Without chunk records it falls back to glove_rowpass_f32 + glove_apply_adagrad_f32. */
 int glove_rowside_step_adagrad_f32(const glove_plan *plan, const glove_tables *t, const glove_hyper *h,
                                    void *ws, size_t ws_bytes, void *stream);
+/* The row side of a step under the optimizer glove_hyper.optimizer names (hyper.sides must be 1; no scalar work: the global
+ * bias, loss and Nadam's momentum cache go with the col side's apply).  Adagrad: glove_rowside_step_adagrad_f32.  Adam, Nadam:
+ * the row pass marks the batch's row ids in G_flat, then one kernel applies the row ids and gives every other row of the row
+ * table its G = 0 update (m and v decay; Adam: the row moves too), clearing the marks.  RMSprop: the row pass, the summed row
+ * gradients into G_flat, the sweep over the row table's rms slot.  SGD, Adamax, Adadelta, Ftrl: the row pass, then their
+ * epilogue on the row ids.  t = global_step as this call's row pass advanced it.  G_flat, all zero on entry and on return:
+ * Adam, Nadam: V_row floats (the marks); RMSprop: the row half [G_R | G_br] of the glove_dense_grad_layout layout for these
+ * tables (the start of a whole dense gradient buffer serves both); unused by Adagrad and the per-row ones.
+ * The row pass's loss partials are left where glove_loss_partials_f32 / glove_dense_grad_f32 look for them.
+ * PRECONDITION as glove_rowside_step_adagrad_f32: the col pass of the step has run. */
+int glove_rowside_step_f32(const glove_plan *plan, const glove_tables *t, const glove_hyper *h,
+                           void *ws, size_t ws_bytes, float *G_flat, void *stream);
 /* GLOVE_STEP_AUTO takes a fused form when (distinct row ids + distinct col ids of the plan) x d x 16 B — the rows a
  * step reads and writes — reaches this many bytes (and the plan carries chunk records or run words); callers that keep a twinned
  * table use the same number to know whether a step may have left versions flipped. */
