@@ -13,6 +13,7 @@
 // a wave64 therefore works on 64/LPR chunks at once.  All sums have a fixed order, so a step is
 // bitwise repeatable for a given plan.
 #include "glove_common.h"
+#include <type_traits>
 
 namespace glove {
 
@@ -1051,6 +1052,32 @@ __device__ inline void loss_from_partials(const float (&tot)[kPartials], const S
     loss = L + k.m * reg;
 }
 
+// The once-per-step scalar work, one thread: from the summed partials `tot` and the global bias with its slots as the step began
+// (from[0], from[1], TWO: from[2]) to the loss scalars (loss_out, unless null) and the bias the next step begins with
+// (to[0 ..]: update(bias, slot 1, slot 2, dg) is the optimizer at hand on the bias gradient dg).
+// CONTRACT_DG = false: dg as a rounded product and a sum of their own (the fused Nadam step has always formed it so)
+template <bool TWO, bool CONTRACT_DG = true, class F>
+__device__ inline void scalar_epilogue(const float (&tot)[kPartials], const StepConsts &k, const float *from, float *to, F update,
+                                       float *loss_out)
+{
+    float gs[3] = {from[0], from[1], TWO ? from[2] : 0.f};
+    const float g = gs[0];
+    float loss, L, reg;
+    loss_from_partials(tot, k, g, loss, L, reg);
+    float dg;
+    if (CONTRACT_DG) {
+        dg = tot[3] + 2.0f * k.m * k.l2 * g;
+    } else {
+#pragma clang fp contract(off)
+        dg = tot[3] + 2.0f * k.m * k.l2 * g;
+    }
+    update(gs[0], gs[1], gs[2], dg);
+    to[0] = gs[0];
+    to[1] = gs[1];
+    if (TWO) to[2] = gs[2];
+    if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
+}
+
 // Behind a FUSE pass most ids are finished: the launch that applies the rest spent its time on one dependent record load
 // per id, 20 ids per lane group in a row (V = 400 k: 57 us for 24 MB of traffic).  One THREAD per distinct id sorts
 // them out first: finished ids of a twinned row table get their version flipped right here, finished ids of the
@@ -1139,17 +1166,9 @@ __global__ __launch_bounds__(kBlock) void apply_adagrad_kernel(
     if (scalar_duty) {
         float tot[kPartials];
         sum_blockpart(blockpart, nblocks_rowpass, tot);
-        if (threadIdx.x == 0) {
-            const float g = scalars[0];
-            float loss, L, reg;
-            loss_from_partials(tot, k, g, loss, L, reg);
-            const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-            float gn = g, Ag = scalars[1];
-            adagrad_elem(gn, Ag, dg, k.lr, k.eps);
-            scalars[1] = Ag;
-            scalars[0] = gn;
-            if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
-        }
+        if (threadIdx.x == 0)
+            scalar_epilogue<false>(tot, k, scalars, scalars, [&](float &gn, float &Ag, float &, float dg) { adagrad_elem(gn, Ag, dg, k.lr, k.eps); },
+                                   loss_out);
     }
     GLOVE_DRAIN(); GLOVE_STAMP(6);
 }
@@ -1449,40 +1468,50 @@ struct OptElem {
 // rows take the epilogue here.  s2: the second slot of every variable where the optimizer has one (scalars[2] for the global bias).
 struct SlotTwo { float *R, *C, *br, *bc; };
 
-constexpr int kSweepRows = 2;       // table rows a sweep lane group keeps in flight (adam_fused_kernel, nadam_fused_kernel,
-                                    // decay_unmarked_kernel)
+constexpr int kSweepRows = 2;       // table rows a sweep lane group keeps in flight (adam_fused_kernel, decay_unmarked_kernel)
 
-// The dense-decay optimizers on the touched-rows exchange: every row NO rank touched (no count bits in its mark — count_packed_kernel
-// marked the lists' ids) takes the G = 0 update; the rows some rank touched are apply_packed_kernel's, the next launch.  Rows
-// [lo, hi) of the concatenation [row side | col side] are swept (the sides glove_hyper.sweep_sides selects).
+// ---- the sweep of the dense-decay optimizers: every row of [lo, hi) of the concatenation [row side | col side] that the step's
+// other workgroups (or its next launch) do not own takes the G = 0 update
 //   Nadam    m and v decay (Keras' legacy sparse Nadam decays them over the whole variable; the row stays)
-//   Adam     m and v decay and the row moves: W -= lr_t m / (sqrt(v) + eps), as adam_fused_kernel's sweep, bit for bit
+//   Adam     m and v decay and the row moves: W -= lr_t m / (sqrt(v) + eps)
 //   RMSprop  the rms slot decays (rho rms + (1 - rho) 0 = rho rms: dense_rmsprop_kernel's bits on a zero gradient)
-// A pure stream: kSweepRows rows in flight per lane group, everything requested before the mark is looked at (what a marked row
-// loaded is dropped), as adam_fused_kernel's sweep.
-template <int LPR, int NV, int OPT>
-__global__ __launch_bounds__(kBlock) void decay_unmarked_kernel(DenseViews dv, SideBufs rs, SideBufs cs, SlotTwo s2, int d4,
-                                                                float b1, float b2, float rho, float lr, float eps, double ln_beta1,
-                                                                double ln_beta2, const int64_t *__restrict__ step, int lo, int hi)
+// A pure stream: a lane group per row, kSweepRows rows in flight per group, everything requested before the mark is looked at
+// (what an owned row loaded is dropped).  Lane group `first` of `stride` takes rows first, first + stride, ...
+// The kind of mark that says who owns a row:
+struct FloatMarks {                 // the fused step: the passes left 1.0f for every id of the batch (in the bias segments of G_flat,
+    float *rows, *cols;             // otherwise unused on this path); the sweep clears it — G_flat is all zero again afterwards
+    typedef float Raw;
+    __device__ Raw load(bool live, bool is_row, int id, int) const { return live ? (is_row ? rows : cols)[id] : 1.0f; }
+    __device__ static bool owned(Raw m) { return m != 0.f; }
+    __device__ void clear(bool is_row, int id) const { (is_row ? rows : cols)[id] = 0.f; }
+};
+struct CountMarks {                 // the touched-rows exchange: count bits in the mark of every id some list names
+    const int32_t *mark;            // (count_packed_kernel); they stay for apply_packed_kernel, the next launch
+    typedef int Raw;
+    __device__ Raw load(bool live, bool, int, int v) const { return live ? mark[v] & kMarkCountMask : 1; }
+    __device__ static bool owned(Raw m) { return m != 0; }
+    __device__ void clear(bool, int) const {}
+};
+
+template <int LPR, int NV, int OPT, class MARKS>
+__device__ inline void sweep_unowned(const MARKS &marks, const SideBufs &rs, const SideBufs &cs, const SlotTwo &s2, int V_row, int d4,
+                                     int first, int stride, int hi, float lr_t, float b1, float b2, float rho, float eps)
 {
-    constexpr int GPB = kBlock / LPR;
     constexpr bool kW = OPT == GLOVE_OPT_ADAM;                  // the row itself moves
     constexpr bool kTwo = OPT != GLOVE_OPT_RMSPROP;             // m and v; RMSprop has its rms only
-    const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    const float lr_t = kW ? adam_lr_t(lr, ln_beta1, ln_beta2, *step) : 0.f;
-    const int stride = gridDim.x * GPB;
-    for (int v0 = lo + blockIdx.x * GPB + grp; v0 < hi; v0 += kSweepRows * stride) {
+    const int lg = threadIdx.x % LPR;
+    for (int v0 = first; v0 < hi; v0 += kSweepRows * stride) {
         f4 Wv[kSweepRows][kW ? NV : 1], M[kSweepRows][NV], Vv[kSweepRows][kTwo ? NV : 1];
-        int mk[kSweepRows];
+        typename MARKS::Raw mk[kSweepRows];
         float bval[kSweepRows], Mb[kSweepRows], Vb[kSweepRows];
 #pragma unroll
         for (int r = 0; r < kSweepRows; ++r) {
             const int v = v0 + r * stride;
             const bool live = v < hi;
-            const bool is_row = v < dv.V_row;
-            const int id = live ? (is_row ? v : v - dv.V_row) : 0;
+            const bool is_row = v < V_row;
+            const int id = live ? (is_row ? v : v - V_row) : 0;
             const SideBufs &sb = is_row ? rs : cs;
-            mk[r] = live ? dv.mark[v] & kMarkCountMask : 1;
+            mk[r] = marks.load(live, is_row, id, v);
             if constexpr (kW) load_row<LPR, NV>(Wv[r], sb.W, id, d4, lg);
             load_row<LPR, NV>(M[r], sb.S1, id, d4, lg);
             if constexpr (kTwo) load_row<LPR, NV>(Vv[r], is_row ? s2.R : s2.C, id, d4, lg);
@@ -1495,11 +1524,15 @@ __global__ __launch_bounds__(kBlock) void decay_unmarked_kernel(DenseViews dv, S
         }
 #pragma unroll
         for (int r = 0; r < kSweepRows; ++r) {
-            if (mk[r]) continue;                                 // past the end, or the apply launch owns this row
             const int v = v0 + r * stride;
-            const bool is_row = v < dv.V_row;
-            const int id = is_row ? v : v - dv.V_row;
+            if (v >= hi) continue;
+            const bool is_row = v < V_row;
+            const int id = is_row ? v : v - V_row;
             const SideBufs &sb = is_row ? rs : cs;
+            if (MARKS::owned(mk[r])) {                           // not this sweep's row
+                if (lg == 0) marks.clear(is_row, id);
+                continue;
+            }
             if constexpr (OPT == GLOVE_OPT_ADAM) {
                 const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1525,6 +1558,19 @@ __global__ __launch_bounds__(kBlock) void decay_unmarked_kernel(DenseViews dv, S
             }
         }
     }
+}
+
+// The dense-decay optimizers on the touched-rows exchange: every row NO rank touched takes the G = 0 update; the rows some rank
+// touched are apply_packed_kernel's, the next launch.  Rows [lo, hi) are swept (the sides glove_hyper.sweep_sides selects).
+template <int LPR, int NV, int OPT>
+__global__ __launch_bounds__(kBlock) void decay_unmarked_kernel(DenseViews dv, SideBufs rs, SideBufs cs, SlotTwo s2, int d4,
+                                                                float b1, float b2, float rho, float lr, float eps, double ln_beta1,
+                                                                double ln_beta2, const int64_t *__restrict__ step, int lo, int hi)
+{
+    constexpr int GPB = kBlock / LPR;
+    const float lr_t = OPT == GLOVE_OPT_ADAM ? adam_lr_t(lr, ln_beta1, ln_beta2, *step) : 0.f;
+    sweep_unowned<LPR, NV, OPT>(CountMarks{dv.mark}, rs, cs, s2, dv.V_row, d4, lo + blockIdx.x * GPB + (int)threadIdx.x / LPR,
+                                gridDim.x * GPB, hi, lr_t, b1, b2, rho, eps);
 }
 
 template <int LPR, int NV, int OPT>
@@ -1654,20 +1700,12 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
                 if (h) { t[0] += h[2]; t[1] += h[3]; t[2] += h[4]; t[3] += h[5]; }
             }
         }
-        const float g = scalars[0];
         const float tot[kPartials] = {t[1], t[2], t[3], t[0]};
-        float loss, L, reg;
-        loss_from_partials(tot, k, g, loss, L, reg);
-        const float dg = t[0] + 2.0f * k.m * k.l2 * g;
-        if constexpr (kAdagrad) {
-            adagrad_elem(scalars[0], scalars[1], dg, k.lr, k.eps);
-        } else {
-            float gn = g, a = scalars[1], b = scalars[2];
-            OptElem<OPT>::one(gn, a, b, dg, o, nk);
-            scalars[0] = gn; scalars[1] = a; scalars[2] = b;
-            if (OPT == GLOVE_OPT_NADAM) scalars[4 + (int)(*step & 1)] = nk.sched_new;      // the momentum cache (see nadam_consts)
-        }
-        if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = t[0]; }
+        scalar_epilogue<!kAdagrad>(tot, k, scalars, scalars, [&](float &gn, float &a, float &b, float dg) {
+            if constexpr (kAdagrad) adagrad_elem(gn, a, dg, k.lr, k.eps);
+            else OptElem<OPT>::one(gn, a, b, dg, o, nk);
+        }, loss_out);
+        if (OPT == GLOVE_OPT_NADAM) scalars[4 + (int)(*step & 1)] = nk.sched_new;      // the momentum cache (see nadam_consts)
     }
 }
 
@@ -1711,7 +1749,7 @@ struct OneSide {
 // which copy (0 / 1) holds the row as it was when step t began
 __device__ inline uint32_t pre_step_copy(uint64_t tag, uint64_t t1 /* 1 + t */) { return (uint32_t)(tag & 1ull) ^ ((tag >> 1) == t1 ? 1u : 0u); }
 
-// A chain record = what one step of a chain leaves for the next: [0] global bias and [1] its accumulator as they were when the
+// A chain record = what one step of a chain leaves for the next: [0] global bias and [1], [2] its slots as they were when the
 // step BEGAN, [8 + 4 b ..] the loss partials of its row-side workgroup b.
 constexpr int kChainHead = 8;
 
@@ -1989,28 +2027,6 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
     if (is_row) {
         part[0] *= 0.5f / inv_batch;        // sum e diff = 2 inv_batch sum w diff^2
         block_partials_store(part, blockpart);
-    }
-}
-
-// The end of a chain of n tagged steps: the last step's loss partials -> the loss scalars and the global bias the NEXT step
-// begins with, into the tables; global_step advances by n.  One workgroup.
-__global__ __launch_bounds__(kBlock) void tagged_flush_kernel(float *__restrict__ scalars, int64_t *__restrict__ step,
-                                                              const float *__restrict__ last, int nblocks, int n, StepConsts k,
-                                                              float *__restrict__ loss_out)
-{
-    float tot[kPartials];
-    sum_blockpart(last + kChainHead, nblocks, tot);
-    if (threadIdx.x == 0) {
-        const float g = last[0];
-        float loss, L, reg;
-        loss_from_partials(tot, k, g, loss, L, reg);
-        const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-        float gn = g, Ag = last[1];
-        adagrad_elem(gn, Ag, dg, k.lr, k.eps);
-        scalars[1] = Ag;
-        scalars[0] = gn;
-        if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
-        *step += n;
     }
 }
 
@@ -2311,24 +2327,26 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_adam_kernel(
     }
 }
 
-// The end of a chain of n one-launch Adam steps: loss, the global bias the next step begins with, which copy is current, global_step
-__global__ __launch_bounds__(kBlock) void tagged_adam_flush_kernel(float *__restrict__ scalars, int64_t *__restrict__ step,
-                                                                   const float *__restrict__ last, int nblocks, int n, StepConsts k,
-                                                                   float b1, float b2, double ln_beta1, double ln_beta2,
-                                                                   float *__restrict__ loss_out)
+// The end of a chain of n one-launch steps: the last step's loss partials -> the loss scalars and the global bias the NEXT step
+// begins with, into the tables; global_step advances by n (Adam: and scalars[3] says which copy is current).  One workgroup.
+template <int OPT>
+__global__ __launch_bounds__(kBlock) void tagged_flush_kernel(float *__restrict__ scalars, int64_t *__restrict__ step,
+                                                              const float *__restrict__ last, int nblocks, int n, StepConsts k,
+                                                              float b1, float b2, double ln_beta1, double ln_beta2,
+                                                              float *__restrict__ loss_out)
 {
     float tot[kPartials];
     sum_blockpart(last + kChainHead, nblocks, tot);
     if (threadIdx.x == 0) {
-        const float g = last[0];
-        float loss, L, reg;
-        loss_from_partials(tot, k, g, loss, L, reg);
-        const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-        float gn = g, Mg = last[1], Vg = last[2];
-        adam_elem(gn, Mg, Vg, dg, adam_lr_t(k.lr, ln_beta1, ln_beta2, *step + n), b1, b2, k.eps);
-        scalars[0] = gn; scalars[1] = Mg; scalars[2] = Vg;
-        if (n & 1) scalars[3] = scalars[3] != 0.f ? 0.f : 1.0f;
-        if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
+        if (OPT == GLOVE_OPT_ADAM) {
+            scalar_epilogue<true>(tot, k, last, scalars, [&](float &gn, float &Mg, float &Vg, float dg) {
+                adam_elem(gn, Mg, Vg, dg, adam_lr_t(k.lr, ln_beta1, ln_beta2, *step + n), b1, b2, k.eps);
+            }, loss_out);
+            if (n & 1) scalars[3] = scalars[3] != 0.f ? 0.f : 1.0f;
+        } else {
+            scalar_epilogue<false>(tot, k, last, scalars, [&](float &gn, float &Ag, float &, float dg) { adagrad_elem(gn, Ag, dg, k.lr, k.eps); },
+                                   loss_out);
+        }
         *step += n;
     }
 }
@@ -2488,7 +2506,7 @@ __global__ __launch_bounds__(kBlock) void dense_adam_kernel(
 template <int LPR, int NV, int OPT>
 struct SparseOptApply {
     SideBufs rs, cs;
-    float *S2_R, *S2_C, *S2_br, *S2_bc;
+    SlotTwo s2;
     int d4, lg;
     OptConsts o;
     struct State { f4 A[NV], B[NV]; float Ab, Bb; };
@@ -2499,11 +2517,10 @@ struct SparseOptApply {
         load_row<LPR, NV>(st.A, sb.S1, id, d4, lg);
         st.Ab = sb.S1b[id];
         if (OptSlots<OPT>::two) {
-            load_row<LPR, NV>(st.B, is_row ? S2_R : S2_C, id, d4, lg);
-            st.Bb = (is_row ? S2_br : S2_bc)[id];
+            load_row<LPR, NV>(st.B, is_row ? s2.R : s2.C, id, d4, lg);
+            st.Bb = (is_row ? s2.br : s2.bc)[id];
         }
     }
-    __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o) { OptElem<OPT>::one(w, a, b, g, o); }
     __device__ void finish(bool is_row, int32_t id, int32_t wid, int q, f4 (&G)[NV], f4 (&Wv)[NV], float Gb, float bval, State &st) const
     {
         const SideBufs &sb = is_row ? rs : cs;
@@ -2514,18 +2531,18 @@ struct SparseOptApply {
             float b[4] = {st.B[kk].x, st.B[kk].y, st.B[kk].z, st.B[kk].w};
             const float g[4] = {G[kk].x, G[kk].y, G[kk].z, G[kk].w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) one(w[i], a[i], b[i], g[i], o);
+            for (int i = 0; i < 4; ++i) OptElem<OPT>::one(w[i], a[i], b[i], g[i], o);
             Wv[kk] = f4{w[0], w[1], w[2], w[3]};
             st.A[kk] = f4{a[0], a[1], a[2], a[3]};
             st.B[kk] = f4{b[0], b[1], b[2], b[3]};
         }
         if (slots) store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, st.A);
-        if (OptSlots<OPT>::two) store_row<LPR, NV>(is_row ? S2_R : S2_C, (size_t)id, d4, lg, st.B);
+        if (OptSlots<OPT>::two) store_row<LPR, NV>(is_row ? s2.R : s2.C, (size_t)id, d4, lg, st.B);
         store_row<LPR, NV>(sb.W, (size_t)wid, d4, lg, Wv);
         if (lg == 0) {
-            one(bval, st.Ab, st.Bb, Gb, o);
+            OptElem<OPT>::one(bval, st.Ab, st.Bb, Gb, o);
             if (slots) sb.S1b[id] = st.Ab;
-            if (OptSlots<OPT>::two) (is_row ? S2_br : S2_bc)[id] = st.Bb;
+            if (OptSlots<OPT>::two) (is_row ? s2.br : s2.bc)[id] = st.Bb;
             sb.bias[wid] = bval;
         }
     }
@@ -2533,27 +2550,20 @@ struct SparseOptApply {
 
 template <int LPR, int NV, int OPT>
 __global__ __launch_bounds__(kBlock) void apply_sparse_opt_kernel(
-    IdWork wk, SideBufs rs, SideBufs cs, float *S2_R, float *S2_C, float *S2_br, float *S2_bc, int d4, StepConsts k, OptConsts o,
+    IdWork wk, SideBufs rs, SideBufs cs, SlotTwo s2, int d4, StepConsts k, OptConsts o,
     double ln_beta1, const int64_t *__restrict__ step, float *__restrict__ scalars, const float *__restrict__ blockpart,
     int nblocks_rowpass, float *__restrict__ loss_out)
 {
     // t = global_step after rowpass advanced it (Adamax: lr_t = lr / (1 - beta1^t))
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
     const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k,
-                                                  SparseOptApply<LPR, NV, OPT>{rs, cs, S2_R, S2_C, S2_br, S2_bc, d4, (int)(threadIdx.x % LPR), o});
+                                                  SparseOptApply<LPR, NV, OPT>{rs, cs, s2, d4, (int)(threadIdx.x % LPR), o});
     if (scalar_duty) {
         float tot[kPartials];
         sum_blockpart(blockpart, nblocks_rowpass, tot);
-        if (threadIdx.x == 0) {
-            const float g = scalars[0];
-            float loss, L, reg;
-            loss_from_partials(tot, k, g, loss, L, reg);
-            const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-            float gn = g, a = scalars[1], b = scalars[2];
-            SparseOptApply<LPR, NV, OPT>::one(gn, a, b, dg, o);
-            scalars[0] = gn; scalars[1] = a; scalars[2] = b;
-            if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
-        }
+        if (threadIdx.x == 0)
+            scalar_epilogue<true>(tot, k, scalars, scalars, [&](float &gn, float &a, float &b, float dg) { OptElem<OPT>::one(gn, a, b, dg, o); },
+                                  loss_out);
     }
 }
 
@@ -2599,227 +2609,89 @@ __global__ __launch_bounds__(kBlock) void dense_rmsprop_kernel(
 // The two parts touch disjoint rows, so they run side by side; only a row's own sweep group reads or clears
 // its mark.  Results are bit-identical to dense_grad + dense_adam; G_flat is all zero again afterwards.
 // ------------------------------------------------------------------------------------------
-template <int LPR, int NV>
-struct AdamApply {
+// (OPT: GLOVE_OPT_ADAM, or GLOVE_OPT_NADAM — Keras-legacy Nadam on the same two-part kernel: the legacy optimizer's sparse path
+// decays m and v over the whole variable like its Adam, but only the touched rows move)
+template <int LPR, int NV, int OPT>
+struct DecayApply {
     SideBufs rs, cs;
-    float *S2_R, *S2_C, *S2_br, *S2_bc;
+    SlotTwo s2;
     int d4, lg;
-    float lr_t, b1, b2, eps;
+    float lr_t, b1, b2, eps;            // Adam
+    NadamConsts nk;                     // Nadam
     struct State { f4 M[NV], V[NV]; float Mb, Vb; };
     __device__ void prefetch(bool is_row, int32_t id, State &st) const
     {
         const SideBufs &sb = is_row ? rs : cs;
         load_row<LPR, NV>(st.M, sb.S1, id, d4, lg);
-        load_row<LPR, NV>(st.V, is_row ? S2_R : S2_C, id, d4, lg);
+        load_row<LPR, NV>(st.V, is_row ? s2.R : s2.C, id, d4, lg);
         st.Mb = sb.S1b[id];
-        st.Vb = (is_row ? S2_br : S2_bc)[id];
-    }
-    __device__ void finish(bool is_row, int32_t id, int32_t wid, int q, f4 (&G)[NV], f4 (&Wv)[NV], float Gb, float bval, State &st) const
-    {
-        const SideBufs &sb = is_row ? rs : cs;
-#pragma unroll
-        for (int kk = 0; kk < NV; ++kk) adam_vec(Wv[kk], st.M[kk], st.V[kk], G[kk], lr_t, b1, b2, eps);
-        store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, st.M);
-        store_row<LPR, NV>(is_row ? S2_R : S2_C, (size_t)id, d4, lg, st.V);
-        store_row<LPR, NV>(sb.W, (size_t)id, d4, lg, Wv);
-        if (lg == 0) {
-            adam_elem(bval, st.Mb, st.Vb, Gb, lr_t, b1, b2, eps);
-            sb.S1b[id] = st.Mb;
-            (is_row ? S2_br : S2_bc)[id] = st.Vb;
-            sb.bias[id] = bval;
-        }
-    }
-};
-
-template <int LPR, int NV>
-struct NadamApply {
-    SideBufs rs, cs;
-    float *S2_R, *S2_C, *S2_br, *S2_bc;
-    int d4, lg;
-    NadamConsts k;
-    struct State { f4 M[NV], V[NV]; float Mb, Vb; };
-    __device__ void prefetch(bool is_row, int32_t id, State &st) const
-    {
-        const SideBufs &sb = is_row ? rs : cs;
-        load_row<LPR, NV>(st.M, sb.S1, id, d4, lg);
-        load_row<LPR, NV>(st.V, is_row ? S2_R : S2_C, id, d4, lg);
-        st.Mb = sb.S1b[id];
-        st.Vb = (is_row ? S2_br : S2_bc)[id];
+        st.Vb = (is_row ? s2.br : s2.bc)[id];
     }
     __device__ void finish(bool is_row, int32_t id, int32_t wid, int q, f4 (&G)[NV], f4 (&Wv)[NV], float Gb, float bval, State &st) const
     {
         const SideBufs &sb = is_row ? rs : cs;
 #pragma unroll
         for (int kk = 0; kk < NV; ++kk) {
-            float w[4] = {Wv[kk].x, Wv[kk].y, Wv[kk].z, Wv[kk].w}, m[4] = {st.M[kk].x, st.M[kk].y, st.M[kk].z, st.M[kk].w};
-            float v[4] = {st.V[kk].x, st.V[kk].y, st.V[kk].z, st.V[kk].w};
-            const float g[4] = {G[kk].x, G[kk].y, G[kk].z, G[kk].w};
+            if constexpr (OPT == GLOVE_OPT_ADAM) {
+                adam_vec(Wv[kk], st.M[kk], st.V[kk], G[kk], lr_t, b1, b2, eps);
+            } else {
+                float w[4] = {Wv[kk].x, Wv[kk].y, Wv[kk].z, Wv[kk].w}, m[4] = {st.M[kk].x, st.M[kk].y, st.M[kk].z, st.M[kk].w};
+                float v[4] = {st.V[kk].x, st.V[kk].y, st.V[kk].z, st.V[kk].w};
+                const float g[4] = {G[kk].x, G[kk].y, G[kk].z, G[kk].w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) nadam_elem(w[i], m[i], v[i], g[i], k);
-            Wv[kk] = f4{w[0], w[1], w[2], w[3]};
-            st.M[kk] = f4{m[0], m[1], m[2], m[3]};
-            st.V[kk] = f4{v[0], v[1], v[2], v[3]};
+                for (int i = 0; i < 4; ++i) nadam_elem(w[i], m[i], v[i], g[i], nk);
+                Wv[kk] = f4{w[0], w[1], w[2], w[3]};
+                st.M[kk] = f4{m[0], m[1], m[2], m[3]};
+                st.V[kk] = f4{v[0], v[1], v[2], v[3]};
+            }
         }
         store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, st.M);
-        store_row<LPR, NV>(is_row ? S2_R : S2_C, (size_t)id, d4, lg, st.V);
+        store_row<LPR, NV>(is_row ? s2.R : s2.C, (size_t)id, d4, lg, st.V);
         store_row<LPR, NV>(sb.W, (size_t)id, d4, lg, Wv);
         if (lg == 0) {
-            nadam_elem(bval, st.Mb, st.Vb, Gb, k);
+            if constexpr (OPT == GLOVE_OPT_ADAM) adam_elem(bval, st.Mb, st.Vb, Gb, lr_t, b1, b2, eps);
+            else nadam_elem(bval, st.Mb, st.Vb, Gb, nk);
             sb.S1b[id] = st.Mb;
-            (is_row ? S2_br : S2_bc)[id] = st.Vb;
+            (is_row ? s2.br : s2.bc)[id] = st.Vb;
             sb.bias[id] = bval;
         }
     }
 };
 
-template <int LPR, int NV>
-__global__ __launch_bounds__(kBlock) void nadam_fused_kernel(
-    IdWork wk, SideBufs rs, SideBufs cs, float *S2_R, float *S2_C, float *S2_br, float *S2_bc, int d4, StepConsts k,
-    float b1, float b2, double ln_beta2, const int64_t *__restrict__ step,
-    float *__restrict__ scalars, const float *__restrict__ blockpart, int nblocks_rowpass,
-    float *__restrict__ mark_rows, float *__restrict__ mark_cols, int V_row, int V, int apply_blocks,
-    float *__restrict__ loss_out)
-{
-#pragma clang fp contract(off)
-    constexpr int GPB = kBlock / LPR;
-    const int lg = threadIdx.x % LPR;
-    const NadamConsts nk = nadam_consts(k.lr, k.eps, b1, b2, ln_beta2, *step, scalars);
-    if ((int)blockIdx.x >= apply_blocks) {
-        // ---- sweep (as adam_fused_kernel's): an unmarked row's m and v decay, the row itself stays; a marked row belongs to the apply part
-        const int grp = threadIdx.x / LPR;
-        const int sb0 = blockIdx.x - apply_blocks, nsb = gridDim.x - apply_blocks;
-        const int total = V_row + V, stride = nsb * GPB;
-        for (int v0 = sb0 * GPB + grp; v0 < total; v0 += kSweepRows * stride) {
-            f4 M[kSweepRows][NV], Vv[kSweepRows][NV];
-            float mk[kSweepRows], Mb[kSweepRows], Vb[kSweepRows];
-#pragma unroll
-            for (int r = 0; r < kSweepRows; ++r) {
-                const int v = v0 + r * stride;
-                const bool live = v < total;
-                const bool is_row = v < V_row;
-                const int id = live ? (is_row ? v : v - V_row) : 0;
-                const SideBufs &sb = is_row ? rs : cs;
-                mk[r] = live ? (is_row ? mark_rows : mark_cols)[id] : 1.0f;
-                load_row<LPR, NV>(M[r], sb.S1, id, d4, lg);
-                load_row<LPR, NV>(Vv[r], is_row ? S2_R : S2_C, id, d4, lg);
-                Mb[r] = Vb[r] = 0.f;
-                if (lg == 0) { Mb[r] = sb.S1b[id]; Vb[r] = (is_row ? S2_br : S2_bc)[id]; }
-            }
-#pragma unroll
-            for (int r = 0; r < kSweepRows; ++r) {
-                const int v = v0 + r * stride;
-                if (v >= total) continue;
-                const bool is_row = v < V_row;
-                const int id = is_row ? v : v - V_row;
-                const SideBufs &sb = is_row ? rs : cs;
-                float *S2 = is_row ? S2_R : S2_C, *S2b = is_row ? S2_br : S2_bc;
-                if (mk[r] != 0.f) {
-                    if (lg == 0) (is_row ? mark_rows : mark_cols)[id] = 0.f;
-                    continue;
-                }
-#pragma unroll
-                for (int kk = 0; kk < NV; ++kk) { M[r][kk] = b1 * M[r][kk]; Vv[r][kk] = b2 * Vv[r][kk]; }
-                store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, M[r]);
-                store_row<LPR, NV>(S2, (size_t)id, d4, lg, Vv[r]);
-                if (lg == 0) { sb.S1b[id] = b1 * Mb[r]; S2b[id] = b2 * Vb[r]; }
-            }
-        }
-        return;
-    }
-    const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k, NadamApply<LPR, NV>{rs, cs, S2_R, S2_C, S2_br, S2_bc, d4, lg, nk},
-                                                  apply_blocks);
-    if (scalar_duty) {
-        float tot[kPartials];
-        sum_blockpart(blockpart, nblocks_rowpass, tot);
-        if (threadIdx.x == 0) {
-            const float g = scalars[0];
-            float loss, L, reg;
-            loss_from_partials(tot, k, g, loss, L, reg);
-            const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-            nadam_elem(scalars[0], scalars[1], scalars[2], dg, nk);
-            scalars[4 + (int)(*step & 1)] = nk.sched_new;
-            if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
-        }
-    }
-}
-
-template <int LPR, int NV>
+template <int LPR, int NV, int OPT>
 __global__ __launch_bounds__(kBlock) void adam_fused_kernel(
-    IdWork wk, SideBufs rs, SideBufs cs, float *S2_R, float *S2_C, float *S2_br, float *S2_bc, int d4, StepConsts k,
+    IdWork wk, SideBufs rs, SideBufs cs, SlotTwo s2, int d4, StepConsts k,
     float b1, float b2, double ln_beta1, double ln_beta2, const int64_t *__restrict__ step,
     float *__restrict__ scalars, const float *__restrict__ blockpart, int nblocks_rowpass,
     float *__restrict__ mark_rows, float *__restrict__ mark_cols, int V_row, int V, int apply_blocks,
     float *__restrict__ loss_out)
 {
     constexpr int GPB = kBlock / LPR;
+    constexpr bool kAdam = OPT == GLOVE_OPT_ADAM;
     const int lg = threadIdx.x % LPR;
-    const float lr_t = adam_lr_t(k.lr, ln_beta1, ln_beta2, *step);
+    const float lr_t = kAdam ? adam_lr_t(k.lr, ln_beta1, ln_beta2, *step) : 0.f;
+    NadamConsts nk = {};
+    if (!kAdam) nk = nadam_consts(k.lr, k.eps, b1, b2, ln_beta2, *step, scalars);
     if ((int)blockIdx.x >= apply_blocks) {
         // ---- sweep: a lane group per table row (R's rows first, then C's), kSweepRows rows in flight per group so
         // that the whole sweep is resident in one round next to the register-heavier apply part
-        const int grp = threadIdx.x / LPR;
         const int sb0 = blockIdx.x - apply_blocks, nsb = gridDim.x - apply_blocks;
-        const int total = V_row + V, stride = nsb * GPB;
-        for (int v0 = sb0 * GPB + grp; v0 < total; v0 += kSweepRows * stride) {
-            f4 Wv[kSweepRows][NV], M[kSweepRows][NV], Vv[kSweepRows][NV];
-            float mk[kSweepRows], bval[kSweepRows], Mb[kSweepRows], Vb[kSweepRows];
-            // everything is requested at once; what a marked row loaded is simply dropped
-#pragma unroll
-            for (int r = 0; r < kSweepRows; ++r) {
-                const int v = v0 + r * stride;
-                const bool live = v < total;
-                const bool is_row = v < V_row;
-                const int id = live ? (is_row ? v : v - V_row) : 0;
-                const SideBufs &sb = is_row ? rs : cs;
-                mk[r] = live ? (is_row ? mark_rows : mark_cols)[id] : 1.0f;
-                load_row<LPR, NV>(Wv[r], sb.W, id, d4, lg);
-                load_row<LPR, NV>(M[r], sb.S1, id, d4, lg);
-                load_row<LPR, NV>(Vv[r], is_row ? S2_R : S2_C, id, d4, lg);
-                bval[r] = Mb[r] = Vb[r] = 0.f;
-                if (lg == 0) { bval[r] = sb.bias[id]; Mb[r] = sb.S1b[id]; Vb[r] = (is_row ? S2_br : S2_bc)[id]; }
-            }
-#pragma unroll
-            for (int r = 0; r < kSweepRows; ++r) {
-                const int v = v0 + r * stride;
-                if (v >= total) continue;
-                const bool is_row = v < V_row;
-                const int id = is_row ? v : v - V_row;
-                const SideBufs &sb = is_row ? rs : cs;
-                float *S2 = is_row ? S2_R : S2_C, *S2b = is_row ? S2_br : S2_bc;
-                if (mk[r] != 0.f) {                              // the apply part owns this row
-                    if (lg == 0) (is_row ? mark_rows : mark_cols)[id] = 0.f;
-                    continue;
-                }
-                const f4 zero = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int kk = 0; kk < NV; ++kk) adam_vec(Wv[r][kk], M[r][kk], Vv[r][kk], zero, lr_t, b1, b2, k.eps);
-                store_row<LPR, NV>(sb.S1, (size_t)id, d4, lg, M[r]);
-                store_row<LPR, NV>(S2, (size_t)id, d4, lg, Vv[r]);
-                store_row<LPR, NV>(sb.W, (size_t)id, d4, lg, Wv[r]);
-                if (lg == 0) {
-                    adam_elem(bval[r], Mb[r], Vb[r], 0.f, lr_t, b1, b2, k.eps);
-                    sb.S1b[id] = Mb[r];
-                    S2b[id] = Vb[r];
-                    sb.bias[id] = bval[r];
-                }
-            }
-        }
+        sweep_unowned<LPR, NV, OPT>(FloatMarks{mark_rows, mark_cols}, rs, cs, s2, V_row, d4, sb0 * GPB + (int)threadIdx.x / LPR, nsb * GPB,
+                                    V_row + V, lr_t, b1, b2, 0.f, k.eps);
         return;
     }
     // ---- apply: the ids of the batch (for_each_id sees a grid of apply_blocks workgroups)
-    const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k,
-                                                  AdamApply<LPR, NV>{rs, cs, S2_R, S2_C, S2_br, S2_bc, d4, lg, lr_t, b1, b2, k.eps},
+    const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k, DecayApply<LPR, NV, OPT>{rs, cs, s2, d4, lg, lr_t, b1, b2, k.eps, nk},
                                                   apply_blocks);
     if (scalar_duty) {
         float tot[kPartials];
         sum_blockpart(blockpart, nblocks_rowpass, tot);
         if (threadIdx.x == 0) {
-            const float g = scalars[0];
-            float loss, L, reg;
-            loss_from_partials(tot, k, g, loss, L, reg);
-            const float dg = tot[3] + 2.0f * k.m * k.l2 * g;
-            adam_elem(scalars[0], scalars[1], scalars[2], dg, lr_t, b1, b2, k.eps);
-            if (loss_out) { loss_out[0] = loss; loss_out[1] = L; loss_out[2] = reg; loss_out[3] = tot[3]; }
+            scalar_epilogue<true, kAdam>(tot, k, scalars, scalars, [&](float &gn, float &m, float &v, float dg) {
+                if constexpr (kAdam) adam_elem(gn, m, v, dg, lr_t, b1, b2, k.eps);
+                else nadam_elem(gn, m, v, dg, nk);
+            }, loss_out);
+            if (!kAdam) scalars[4 + (int)(*step & 1)] = nk.sched_new;      // the momentum cache (see nadam_consts)
         }
     }
 }
@@ -2827,8 +2699,6 @@ __global__ __launch_bounds__(kBlock) void adam_fused_kernel(
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static inline RowShape pass_shape(int d4) { return pick_pass_shape(d4); }
-
 static int check_common(const glove_plan *p, const glove_tables *t, const glove_hyper *h, const void *ws)
 {
     if (!p || !t || !h || !ws) return GLOVE_E_BADARG;
@@ -2841,7 +2711,7 @@ static int check_common(const glove_plan *p, const glove_tables *t, const glove_
     const bool own_pairs = p->r_partner && p->r_w && p->r_y && p->c_partner && p->c_w && p->c_y;
     if (p->B > 0 && !own_pairs && !(p->r_crec && p->c_crec)) return GLOVE_E_BADARG;
     const RowShape shape = pick_row_shape(t->d / 4);
-    if (shape.lpr == 0 || pass_shape(t->d / 4).lpr == 0 || p->chunk_cap <= 0) return GLOVE_E_BADARG;
+    if (shape.lpr == 0 || pick_pass_shape(t->d / 4).lpr == 0 || p->chunk_cap <= 0) return GLOVE_E_BADARG;
     if ((uint64_t)t->V * (uint64_t)t->d * 4u >= (1ull << 32) || t->V_row < 0 || t->V_row > t->V) return GLOVE_E_BADARG;   // 32-bit row offsets
     if (t->R_ver && 2ull * (uint64_t)(t->V_row > 0 ? t->V_row : t->V) * (uint64_t)t->d * 4u >= (1ull << 32)) return GLOVE_E_BADARG;
     if ((t->R_tag != nullptr) != (t->C_tag != nullptr) || (t->R_tag && t->R_ver)) return GLOVE_E_BADARG;   // tags: both tables, not beside R_ver
@@ -2888,6 +2758,12 @@ static IdWork id_work(const glove_plan *p)
     return w;
 }
 
+// the grid of an apply launch (for_each_id): the heavy ids' workgroups, the light ids' lane groups, one workgroup of scalar duty
+static inline int apply_blocks(const glove_plan *p, RowShape shape)
+{
+    return id_work(p).heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
+}
+
 static StepConsts make_consts(const glove_tables *t, const glove_hyper *h)
 {
     StepConsts k;
@@ -2901,6 +2777,49 @@ static StepConsts make_consts(const glove_tables *t, const glove_hyper *h)
     k.inv_batch = h->inv_batch;
     k.inv_d = 1.0f / dm;
     return k;
+}
+
+// The optimizer's own hyper-parameters as the apply kernels take them; the logs of the betas in fp64 (adam_lr_t)
+struct OptHyper { OptConsts o; float b1, b2; double ln_b1, ln_b2; };
+static OptHyper opt_consts(const glove_hyper *h)
+{
+    OptHyper x;
+    x.b1 = (float)h->beta1;
+    x.b2 = (float)h->beta2;
+    x.o = {h->learning_rate, h->epsilon, h->momentum, 0.f, x.b1, x.b2, h->nesterov ? 1 : 0, h->rho};
+    // (an optimizer without betas leaves them unchecked, and its kernels do not read the logs: 0 then, as for a beta out of range)
+    x.ln_b1 = x.b1 > 0.f ? log((double)x.b1) : 0.0;
+    x.ln_b2 = x.b2 > 0.f ? log((double)x.b2) : 0.0;
+    return x;
+}
+
+// Optimizer `opt` (glove_hyper.optimizer, or the one an entry point stands for) on `sides` (1 rows, 2 cols, 3 both): its slots are
+// there and its hyper-parameters are in range
+static int check_optimizer(const glove_tables *t, const glove_hyper *h, int sides, int opt)
+{
+    const bool betas = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM;
+    const bool two_slots = betas || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL;
+    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && !two_slots) return GLOVE_E_BADARG;
+    if ((sides & 1) && (!t->s1_R || !t->s1_br || (two_slots && (!t->s2_R || !t->s2_br)))) return GLOVE_E_BADARG;
+    if ((sides & 2) && (!t->s1_C || !t->s1_bc || (two_slots && (!t->s2_C || !t->s2_bc)))) return GLOVE_E_BADARG;
+    if (betas && (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0) || !t->step)) return GLOVE_E_BADARG;
+    if ((opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_RMSPROP) && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+    if (opt == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
+    if (opt == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
+    return 0;
+}
+
+// A run-time optimizer as the compile-time OPT of a launch: f(std::integral_constant<int, OPT>) for the one of OPTS that opt is
+template <int... OPTS, class F>
+static bool dispatch_opt(int opt, F f)
+{
+    return ((opt == OPTS ? (f(std::integral_constant<int, OPTS>{}), true) : false) || ...);
+}
+// ... and a run-time condition (rows that fill their lanes: LPR * NV == d4 -> FULL) as a compile-time bool
+template <class F>
+static void dispatch_bool(bool on, F f)
+{
+    if (on) f(std::true_type{}); else f(std::false_type{});
 }
 
 static inline int rowpass_blocks(const glove_plan *p, int lpr) { return blocks_for(p->cap_chunks, kBlock / lpr); }
@@ -2961,6 +2880,37 @@ static SideBufs side_bufs(const glove_plan *p, const StepWs &w, const glove_tabl
     s.twin = 0;
     return s;
 }
+
+// One side of a one-launch step: S = OneSide (Adagrad: the step tags) or AdamSide (the second slot, the bitmap of the batch's ids)
+template <class S>
+static S step_side(const glove_plan *p, const glove_tables *t, bool row)
+{
+    S s;
+    s.crec = row ? p->r_crec : p->c_crec;
+    s.own = row ? t->R : t->C;
+    s.own_bias = row ? t->br : t->bc;
+    s.other = row ? t->C : t->R;
+    s.other_bias = row ? t->bc : t->br;
+    s.S1 = row ? t->s1_R : t->s1_C;
+    s.S1b = row ? t->s1_br : t->s1_bc;
+    if constexpr (std::is_same<S, AdamSide>::value) {
+        s.S2 = row ? t->s2_R : t->s2_C;
+        s.S2b = row ? t->s2_br : t->s2_bc;
+        s.mark = row ? p->r_mark : p->c_mark;
+    } else {
+        s.own_tag = row ? t->R_tag : t->C_tag;
+        s.other_tag = row ? t->C_tag : t->R_tag;
+    }
+    s.own_twin = row ? v_row(t) : t->V;
+    s.other_twin = row ? t->V : v_row(t);
+    s.n_host = p->host_counts[row ? 0 : 2];
+    s.count_index = row ? 0 : 2;
+    s.capP = rec_cap(p->chunk_cap);
+    s.cap_chunks = p->cap_chunks > 0 ? p->cap_chunks : 1;
+    return s;
+}
+
+static inline SlotTwo slot_two(const glove_tables *t) { return SlotTwo{t->s2_R, t->s2_C, t->s2_br, t->s2_bc}; }
 
 }  // namespace glove
 
@@ -3044,7 +2994,7 @@ static int launch_passes(const glove_plan *p, const glove_tables *t, const glove
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
     if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
     const int d4 = t->d / 4;
-    const RowShape shape = pass_shape(d4);
+    const RowShape shape = pick_pass_shape(d4);
     const int per = fuse ? fuse_per(p, shape.lpr) : 1;
     const int row_blocks = !(which & 1) ? 0 : fuse ? fusepass_blocks(p, shape.lpr, per, true) : rowpass_blocks(p, shape.lpr);
     const int nb = row_blocks + (!(which & 2) ? 0 : fuse ? fusepass_blocks(p, shape.lpr, per, false) : rowpass_blocks(p, shape.lpr));
@@ -3108,13 +3058,11 @@ static int launch_passes(const glove_plan *p, const glove_tables *t, const glove
             K(LPR, NV, FULL, REC, FUSE, -1, -1, nb);                                                                             \
     } while (0)
 #define CALL(LPR, NV)                                                                   \
-    if (LPR * NV == d4) {                                                               \
-        if (rec) { if (pack) LAUNCH(LPR, NV, true, true, 2); else if (fuse) LAUNCH(LPR, NV, true, true, 1); else LAUNCH(LPR, NV, true, true, 0); } \
-        else { if (fuse) LAUNCH(LPR, NV, true, false, 1); else LAUNCH(LPR, NV, true, false, 0); }        \
-    } else {                                                                            \
-        if (rec) { if (pack) LAUNCH(LPR, NV, false, true, 2); else if (fuse) LAUNCH(LPR, NV, false, true, 1); else LAUNCH(LPR, NV, false, true, 0); } \
-        else { if (fuse) LAUNCH(LPR, NV, false, false, 1); else LAUNCH(LPR, NV, false, false, 0); }      \
-    }
+    dispatch_bool(LPR * NV == d4, [&](auto full) {                                      \
+        constexpr bool FULL = decltype(full)::value;                                    \
+        if (rec) { if (pack) LAUNCH(LPR, NV, FULL, true, 2); else if (fuse) LAUNCH(LPR, NV, FULL, true, 1); else LAUNCH(LPR, NV, FULL, true, 0); } \
+        else { if (fuse) LAUNCH(LPR, NV, FULL, false, 1); else LAUNCH(LPR, NV, FULL, false, 0); }        \
+    })
     GLOVE_DISPATCH_PASS_SHAPE(shape, CALL);
 #undef CALL
 #undef LAUNCH
@@ -3158,11 +3106,11 @@ static int launch_apply_adagrad(const glove_plan *p, const glove_tables *t, cons
     wk.pre_r = pre_r;
     wk.pre_c = pre_c;
     const bool fused = pre_r != kFuseNone || pre_c != kFuseNone;
-    wk.per = fused ? fuse_per(p, pass_shape(d4).lpr) : 1;
-    wk.gpb = fused && solid_groups(p) ? kBlock / pass_shape(d4).lpr : 0;
-    const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
+    wk.per = fused ? fuse_per(p, pick_pass_shape(d4).lpr) : 1;
+    wk.gpb = fused && solid_groups(p) ? kBlock / pick_pass_shape(d4).lpr : 0;
+    const int nb = apply_blocks(p, shape);
     // workgroups of the row-side pass, whose loss partials the scalar duty sums (the first launch of the step)
-    const int nb_row = fused ? fusepass_blocks(p, pass_shape(d4).lpr, wk.per, true) : rowpass_blocks(p, pass_shape(d4).lpr);
+    const int nb_row = fused ? fusepass_blocks(p, pick_pass_shape(d4).lpr, wk.per, true) : rowpass_blocks(p, pick_pass_shape(d4).lpr);
     const StepConsts k = make_consts(t, h);
     SideBufs rs = side_bufs(p, w, t, true);
     const SideBufs cs = side_bufs(p, w, t, false);
@@ -3217,8 +3165,8 @@ static int launch_dense_grad(const glove_plan *p, const glove_tables *t, const g
     const RowShape shape = pick_row_shape(d4);
     IdWork wk = id_work(p);
     wk.sides = sides_of(h);
-    const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
-    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
+    const int nb = apply_blocks(p, shape);
+    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
     const StepConsts k = make_consts(t, h);
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
     const GradLayout L = grad_layout(v_row(t), t->V, t->d);
@@ -3314,8 +3262,8 @@ int glove_pack_grad_f32(const glove_plan *p, const glove_tables *t, const glove_
     if (1 + nr + nc > capacity_entries) return GLOVE_E_WORKSPACE;
     const int d4 = t->d / 4;
     const RowShape shape = pick_row_shape(d4);
-    const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
-    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
+    const int nb = apply_blocks(p, shape);
+    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
     const StepConsts k = make_consts(t, h);
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
     hipStream_t st = (hipStream_t)stream;
@@ -3364,11 +3312,11 @@ int glove_pack_rest_f32(const glove_plan *p, const glove_tables *t, const glove_
     if (1 + nr + nc > capacity_entries) return GLOVE_E_WORKSPACE;
     const int d4 = t->d / 4;
     const RowShape shape = pick_row_shape(d4);
-    const int lpr = pass_shape(d4).lpr;
+    const int lpr = pick_pass_shape(d4).lpr;
     wk.pre_r = (wk.sides & 1) ? kFusePack : kFuseNone;
     wk.pre_c = (wk.sides & 2) ? kFusePack : kFuseNone;
     wk.per = fuse_per(p, lpr);
-    const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
+    const int nb = apply_blocks(p, shape);
     // the loss partials: of the packing row pass (its grid), or folded by glove_rowside_step_adagrad_f32 (any count reads them)
     const int nb_row = fusepass_blocks(p, lpr, wk.per, true);
     const StepConsts k = make_consts(t, h);
@@ -3387,7 +3335,7 @@ int glove_loss_partials_f32(const glove_plan *p, const glove_tables *t, void *ws
     if (!p || !t || !ws || !out4 || t->d <= 0 || (t->d % 4) != 0) return GLOVE_E_BADARG;
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
     if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    const int lpr = pass_shape(t->d / 4).lpr;
+    const int lpr = pick_pass_shape(t->d / 4).lpr;
     if (lpr == 0) return GLOVE_E_BADARG;
     // the grid of the row pass that left them (folded by glove_rowside_step_adagrad_f32: any count reads the same)
     const int nb_row = packing_ok(p) ? fusepass_blocks(p, lpr, fuse_per(p, lpr), true) : rowpass_blocks(p, lpr);
@@ -3460,25 +3408,15 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
     DenseViews dv;
     if (int rc = packed_common(t, G_flat, mark, dv)) return rc;
     if (!h || !lists || n_lists < 1 || capacity_entries < 0) return GLOVE_E_BADARG;
-    if (!t->R || !t->C || !t->br || !t->bc || !t->scalars || !t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc) return GLOVE_E_BADARG;
+    if (!t->R || !t->C || !t->br || !t->bc || !t->scalars) return GLOVE_E_BADARG;
     // glove_hyper.optimizer: Adagrad, one of the per-row Keras optimizers (only touched rows move: the exchange is the same), or
     // a dense-decay one (Nadam, Adam, RMSprop: the sweep below moves the slots — Adam: the rows too — of every row no list names)
     const int opt = h->optimizer;
-    const bool two_slots = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL || opt == GLOVE_OPT_NADAM ||
-                           opt == GLOVE_OPT_ADAM;
     const bool decays = opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_RMSPROP;
-    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && !two_slots) return GLOVE_E_BADARG;
-    if (two_slots && (!t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)) return GLOVE_E_BADARG;
-    if ((opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM) &&
-        (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0) || !t->step)) return GLOVE_E_BADARG;
-    if ((opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_RMSPROP) && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+    if (int rc = check_optimizer(t, h, 3, opt)) return rc;
     if (h->sweep_sides < 0 || h->sweep_sides > 3) return GLOVE_E_BADARG;
-    if (opt == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
-    if (opt == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
-    const OptConsts o = {h->learning_rate, h->epsilon, h->momentum, 0.f, (float)h->beta1, (float)h->beta2, h->nesterov ? 1 : 0, h->rho};
-    const double ln_b1 = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADAM ? log((double)(float)h->beta1) : 0.0;
-    const double ln_b2 = opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM ? log((double)(float)h->beta2) : 0.0;
-    const SlotTwo s2 = {t->s2_R, t->s2_C, t->s2_br, t->s2_bc};
+    const OptHyper oh = opt_consts(h);
+    const SlotTwo s2 = slot_two(t);
     if (int rc = plain_table(t, stream)) return rc;
     const int d4 = t->d / 4;
     const RowShape shape = pick_row_shape(d4);
@@ -3508,17 +3446,14 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         const int sweep = h->sweep_sides ? h->sweep_sides : sides_of(h);
         const int lo = (sweep & 1) ? 0 : v_row(t), hi = (sweep & 2) ? v_row(t) + t->V : v_row(t);
         const int nbd = blocks_for(((int64_t)(hi - lo) + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
-        const float b1 = (float)h->beta1, b2 = (float)h->beta2;
-#define LAUNCH_OPT(LPR, NV, OPT)                                                                                      \
-        hipLaunchKernelGGL((decay_unmarked_kernel<LPR, NV, OPT>), dim3(nbd), dim3(kBlock), 0, st, dv, rs, cs, s2, d4, b1, b2, \
-                           h->rho, h->learning_rate, h->epsilon, ln_b1, ln_b2, (const int64_t *)t->step, lo, hi)
-#define CALL(LPR, NV)                                                                                                 \
-        if (opt == GLOVE_OPT_ADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAM);                                               \
-        else if (opt == GLOVE_OPT_RMSPROP) LAUNCH_OPT(LPR, NV, GLOVE_OPT_RMSPROP);                                    \
-        else LAUNCH_OPT(LPR, NV, GLOVE_OPT_NADAM)
+#define CALL(LPR, NV)                                                                                                         \
+        dispatch_opt<GLOVE_OPT_ADAM, GLOVE_OPT_RMSPROP, GLOVE_OPT_NADAM>(opt, [&](auto o_) {                                  \
+            hipLaunchKernelGGL((decay_unmarked_kernel<LPR, NV, decltype(o_)::value>), dim3(nbd), dim3(kBlock), 0, st, dv, rs, cs, s2, \
+                               d4, oh.b1, oh.b2, h->rho, h->learning_rate, h->epsilon, oh.ln_b1, oh.ln_b2,                    \
+                               (const int64_t *)t->step, lo, hi);                                                             \
+        })
         if (hi > lo) GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
-#undef LAUNCH_OPT
     }
     for (int32_t first = 0; first < n_lists; first += 8) {
         PackedLists pls;
@@ -3531,20 +3466,14 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         }
         const int nbx = blocks_for(n_max > 0 ? n_max : 1, kBlock / shape.lpr);
         const int scal = first == 0 ? do_scalars : 0;
-#define LAUNCH_OPT(LPR, NV, OPT)                                                                                     \
-        hipLaunchKernelGGL((apply_packed_kernel<LPR, NV, OPT>), dim3(nbx, pls.n), dim3(kBlock), 0, st, pls, dv, rs, cs, s2, \
-                           d4, k, o, ln_b1, ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars, loss_out, scal)
-#define CALL(LPR, NV)                                                                                               \
-        if (opt == GLOVE_OPT_ADAGRAD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAGRAD);                                       \
-        else if (opt == GLOVE_OPT_SGD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_SGD);                                          \
-        else if (opt == GLOVE_OPT_ADAMAX) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAMAX);                                    \
-        else if (opt == GLOVE_OPT_ADADELTA) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADADELTA);                                \
-        else if (opt == GLOVE_OPT_NADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_NADAM);                                      \
-        else if (opt == GLOVE_OPT_ADAM) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAM);                                        \
-        else if (opt == GLOVE_OPT_RMSPROP) LAUNCH_OPT(LPR, NV, GLOVE_OPT_RMSPROP);                                  \
-        else LAUNCH_OPT(LPR, NV, GLOVE_OPT_FTRL)
+#define CALL(LPR, NV)                                                                                                         \
+        dispatch_opt<GLOVE_OPT_ADAGRAD, GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_NADAM, GLOVE_OPT_ADAM,  \
+                     GLOVE_OPT_RMSPROP, GLOVE_OPT_FTRL>(opt, [&](auto o_) {                                                   \
+            hipLaunchKernelGGL((apply_packed_kernel<LPR, NV, decltype(o_)::value>), dim3(nbx, pls.n), dim3(kBlock), 0, st, pls, dv, rs, \
+                               cs, s2, d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars,    \
+                               loss_out, scal);                                                                               \
+        })
         GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
-#undef LAUNCH_OPT
 #undef CALL
     }
     if (scratch) {
@@ -3612,61 +3541,81 @@ static int pick_step_form(const glove_plan *p, const glove_tables *t, const glov
     return t->R_ver ? GLOVE_STEP_FUSED_TWIN : GLOVE_STEP_FUSED_THREE_LAUNCH;
 }
 
-// n consecutive tagged steps as chains: one launch per step, the global bias handed from step to step through chain records in
-// the workspace (the tagged form keeps nothing else there: no partial rows), one epilogue launch per chain.
+// Whether an Adam step takes the one-launch form (tagged_adam_kernel): twinned tables (glove_tables.R_tag / C_tag are the
+// sign; the tags themselves stay zero), a plan with chunk records and id bitmaps, a small batch that touches a minority of the rows
+static bool adam_one_launch(const glove_plan *p, const glove_tables *t, const glove_hyper *h)
+{
+    if (!p || !t || !h || sides_of(h) != 3) return false;
+    if (!t->R_tag || !t->C_tag || !p->r_crec || !p->c_crec || !p->r_mark || !p->c_mark) return false;
+    if (h->step_form != GLOVE_STEP_AUTO && h->step_form != GLOVE_STEP_TAGGED) return false;
+    if (h->step_form == GLOVE_STEP_AUTO && p->host_counts[4] > 0) return false;     // heavy ids: as pick_step_form
+    return p->B <= 2048 && 2 * p->B <= (int64_t)v_row(t) + t->V;
+}
+
+// n consecutive one-launch steps (opt: GLOVE_OPT_ADAGRAD on step-tagged tables, GLOVE_OPT_ADAM on twins flipped as a whole) as
+// chains: one launch per step, the global bias handed from step to step through chain records in the workspace (the one-launch
+// forms keep nothing else there: no partial rows), one epilogue launch per chain.
 static int launch_tagged_chain(const glove_plan *const *plans, int n, const glove_tables *t, const glove_hyper *h, void *ws,
-                               size_t ws_bytes, float *loss_out, void *stream)
+                               size_t ws_bytes, float *loss_out, void *stream, int opt)
 {
     if (!plans || n < 1 || !t || !h || !ws) return GLOVE_E_BADARG;
+    const bool adam = opt == GLOVE_OPT_ADAM;
     const int d4 = t->d / 4;
     int most_blocks = 1;
     for (int i = 0; i < n; ++i) {
         const glove_plan *p = plans[i];
         if (int rc = check_common(p, t, h, ws)) return rc;
-        if (!t->R_tag || !t->C_tag || !p->r_crec || !p->c_crec) return GLOVE_E_BADARG;
-        const int rb = rowpass_blocks(p, pass_shape(d4).lpr);
+        if (adam ? !adam_one_launch(p, t, h) : (!t->R_tag || !t->C_tag || !p->r_crec || !p->c_crec)) return GLOVE_E_BADARG;
+        const int rb = rowpass_blocks(p, pick_pass_shape(d4).lpr);
         most_blocks = rb > most_blocks ? rb : most_blocks;
     }
-    if (!t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc || sides_of(h) != 3) return GLOVE_E_BADARG;
+    if (sides_of(h) != 3) return GLOVE_E_BADARG;
+    if (int rc = check_optimizer(t, h, 3, opt)) return rc;
     const size_t rec_floats = (size_t)kChainHead + (size_t)kPartials * most_blocks;
     const size_t fit = ws_bytes / (rec_floats * sizeof(float));
     if (fit < 1) return GLOVE_E_WORKSPACE;
-    const RowShape shape = pass_shape(d4);
-    const int Vr = v_row(t);
+    const RowShape shape = pick_pass_shape(d4);
     const StepConsts kc = make_consts(t, h);
+    const OptHyper oh = opt_consts(h);
     hipStream_t st = (hipStream_t)stream;
     float *recs = (float *)ws;
+    // Adam's sweep over all other rows: its part of the grid as adam_fused_kernel's, behind a multiple of 8 workgroups, so that
+    // every step's sweep finds the rows it wrote last step in the same L2s
+    const int sweep_rows = tagged_sweep_rows(shape.nv);
+    const int sweep_blocks = adam ? blocks_for(((int64_t)v_row(t) + t->V + sweep_rows - 1) / sweep_rows, kBlock / shape.lpr) : 0;
     for (int i0 = 0; i0 < n; i0 += (int)fit) {
         const int m = n - i0 < (int)fit ? n - i0 : (int)fit;
         int prev_blocks = 0;
         for (int i = 0; i < m; ++i) {
             const glove_plan *p = plans[i0 + i];
-            const int row_blocks = rowpass_blocks(p, shape.lpr), nb = 2 * row_blocks;     // the classic passes' grid and chunk assignment
-            OneSide rs, cs;
-            rs.crec = p->r_crec; rs.own = t->R; rs.own_bias = t->br; rs.other = t->C; rs.other_bias = t->bc;
-            rs.S1 = t->s1_R; rs.S1b = t->s1_br; rs.own_tag = t->R_tag; rs.other_tag = t->C_tag; rs.own_twin = Vr; rs.other_twin = t->V;
-            rs.n_host = p->host_counts[0]; rs.count_index = 0; rs.capP = rec_cap(p->chunk_cap);
-            cs.crec = p->c_crec; cs.own = t->C; cs.own_bias = t->bc; cs.other = t->R; cs.other_bias = t->br;
-            cs.S1 = t->s1_C; cs.S1b = t->s1_bc; cs.own_tag = t->C_tag; cs.other_tag = t->R_tag; cs.own_twin = t->V; cs.other_twin = Vr;
-            cs.n_host = p->host_counts[2]; cs.count_index = 2; cs.capP = rs.capP;
-            rs.cap_chunks = cs.cap_chunks = p->cap_chunks > 0 ? p->cap_chunks : 1;
+            // the classic passes' grid and chunk assignment
+            const int row_blocks = rowpass_blocks(p, shape.lpr), chunk_blocks = adam ? (2 * row_blocks + 7) & ~7 : 2 * row_blocks;
+            const int nb = chunk_blocks + sweep_blocks;
             const float *prev = i > 0 ? recs + (size_t)(i - 1) * rec_floats : nullptr;
             float *mine = recs + (size_t)i * rec_floats;
 #define CALL(LPR, NV)                                                                                                           \
-            if (LPR * NV == d4)                                                                                                 \
-                hipLaunchKernelGGL((tagged_step_kernel<LPR, NV, true>), dim3(nb), dim3(kBlock), 0, st, p->counts, rs, cs, row_blocks, \
-                                   (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head,        \
-                                   h->neg_factor, kc, prev, prev_blocks, mine, i);                                             \
-            else                                                                                                                \
-                hipLaunchKernelGGL((tagged_step_kernel<LPR, NV, false>), dim3(nb), dim3(kBlock), 0, st, p->counts, rs, cs, row_blocks, \
-                                   (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head,        \
-                                   h->neg_factor, kc, prev, prev_blocks, mine, i)
+            dispatch_bool(LPR * NV == d4, [&](auto full) {                                                                      \
+                constexpr bool FULL = decltype(full)::value;                                                                    \
+                if (adam)                                                                                                       \
+                    hipLaunchKernelGGL((tagged_adam_kernel<LPR, NV, FULL>), dim3(nb), dim3(kBlock), 0, st, p->counts,           \
+                                       step_side<AdamSide>(p, t, true), step_side<AdamSide>(p, t, false), row_blocks,           \
+                                       chunk_blocks, (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head, \
+                                       h->neg_factor, kc, oh.b1, oh.b2, oh.ln_b1, oh.ln_b2, prev, prev_blocks, mine, i);        \
+                else                                                                                                            \
+                    hipLaunchKernelGGL((tagged_step_kernel<LPR, NV, FULL>), dim3(nb), dim3(kBlock), 0, st, p->counts,           \
+                                       step_side<OneSide>(p, t, true), step_side<OneSide>(p, t, false), row_blocks,             \
+                                       (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head,    \
+                                       h->neg_factor, kc, prev, prev_blocks, mine, i);                                         \
+            })
             GLOVE_DISPATCH_PASS_SHAPE(shape, CALL);
 #undef CALL
             prev_blocks = row_blocks;
         }
-        hipLaunchKernelGGL(tagged_flush_kernel, dim3(1), dim3(kBlock), 0, st, t->scalars, t->step,
-                           (const float *)(recs + (size_t)(m - 1) * rec_floats), prev_blocks, m, kc, i0 + m == n ? loss_out : nullptr);
+        const float *last = recs + (size_t)(m - 1) * rec_floats;
+        dispatch_opt<GLOVE_OPT_ADAGRAD, GLOVE_OPT_ADAM>(opt, [&](auto o_) {
+            hipLaunchKernelGGL((tagged_flush_kernel<decltype(o_)::value>), dim3(1), dim3(kBlock), 0, st, t->scalars, t->step, last, prev_blocks,
+                               m, kc, oh.b1, oh.b2, oh.ln_b1, oh.ln_b2, i0 + m == n ? loss_out : nullptr);
+        });
     }
     return (int)hipGetLastError();
 }
@@ -3675,7 +3624,7 @@ int glove_step_adagrad_f32(const glove_plan *p, const glove_tables *t, const glo
                            float *loss_out, void *stream)
 {
     const int form = pick_step_form(p, t, h);
-    if (form == GLOVE_STEP_TAGGED) return launch_tagged_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream);
+    if (form == GLOVE_STEP_TAGGED) return launch_tagged_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAGRAD);
     // only the twin form follows the version bytes of a twinned row table: every other form first brings it home
     // (a step of another form behind a twin step would otherwise read and write copy 0 of rows whose current copy is the second)
     if (form != GLOVE_STEP_FUSED_TWIN)
@@ -3726,7 +3675,7 @@ int glove_rowside_step_adagrad_f32(const glove_plan *p, const glove_tables *t, c
     if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1, nullptr, nullptr, false, kFuseInPlace, kFuseNone)) return rc;
     if (int rc = launch_apply_adagrad(p, t, h, ws, ws_bytes, nullptr, stream, kFuseInPlace, kFuseNone)) return rc;
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    const int lpr = pass_shape(t->d / 4).lpr;
+    const int lpr = pick_pass_shape(t->d / 4).lpr;
     const int nb_fused = fusepass_blocks(p, lpr, fuse_per(p, lpr), true);
     hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, w.blockpart, nb_fused);
     return (int)hipGetLastError();
@@ -3776,7 +3725,7 @@ int glove_steps_adagrad_f32(const glove_plan *const *plans, int32_t n, const glo
         int32_t k = i;
         while (k < n && plans[k] && pick_step_form(plans[k], t, h) == GLOVE_STEP_TAGGED) ++k;
         if (k > i) {
-            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream)) return rc;
+            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream, GLOVE_OPT_ADAGRAD)) return rc;
             i = k;
             continue;
         }
@@ -3793,9 +3742,8 @@ static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glo
                            float *G_flat, float *loss_out, void *stream, bool nadam = false, int which = 3)
 {
     if (int rc = check_common(p, t, h, ws)) return rc;
-    if (!G_flat || !t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc || !t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)
-        return GLOVE_E_BADARG;
-    if (!(h->beta1 > 0.0 && h->beta1 < 1.0 && h->beta2 > 0.0 && h->beta2 < 1.0)) return GLOVE_E_BADARG;
+    if (!G_flat) return GLOVE_E_BADARG;
+    if (int rc = check_optimizer(t, h, 3, nadam ? GLOVE_OPT_NADAM : GLOVE_OPT_ADAM)) return rc;     // (both sides' slots, whichever step)
     const int32_t Vr = v_row(t);
     const GradLayout L = grad_layout(Vr, t->V, t->d);
     float *mark_rows = which & 2 ? G_flat + L.G_br : G_flat, *mark_cols = which & 2 ? G_flat + L.G_bc : nullptr;
@@ -3808,23 +3756,19 @@ static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glo
     const int32_t Vc = which & 2 ? t->V : 0;         // col rows the sweep covers (behind R's rows)
     // a multiple of 8 workgroups in front: workgroups b and b + 8 share an XCD, so every step's sweep then finds
     // the rows it wrote last step in the same L2s, whatever the batch's id count (5.3 vs 11 us per launch)
-    const int apply_blocks = (wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1 + 7) & ~7;
-    const int nb = apply_blocks + blocks_for(((int64_t)Vr + Vc + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
-    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
+    const int nb_apply = (apply_blocks(p, shape) + 7) & ~7;
+    const int nb = nb_apply + blocks_for(((int64_t)Vr + Vc + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
+    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
     const StepConsts k = make_consts(t, h);
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
+    const OptHyper oh = opt_consts(h);
     hipStream_t st = (hipStream_t)stream;
-#define CALL(LPR, NV)                                                                                          \
-    if (nadam)                                                                                                 \
-        hipLaunchKernelGGL((nadam_fused_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
-                           t->s2_br, t->s2_bc, d4, k, (float)h->beta1, (float)h->beta2, log((double)(float)h->beta2), \
-                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc,   \
-                           apply_blocks, loss_out);                                                            \
-    else                                                                                                       \
-        hipLaunchKernelGGL((adam_fused_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
-                           t->s2_br, t->s2_bc, d4, k, (float)h->beta1, (float)h->beta2, log((double)(float)h->beta1), log((double)(float)h->beta2),  \
-                           t->step, t->scalars, w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc,   \
-                           apply_blocks, loss_out)
+#define CALL(LPR, NV)                                                                                                  \
+    dispatch_opt<GLOVE_OPT_ADAM, GLOVE_OPT_NADAM>(nadam ? GLOVE_OPT_NADAM : GLOVE_OPT_ADAM, [&](auto o_) {            \
+        hipLaunchKernelGGL((adam_fused_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, slot_two(t), \
+                           d4, k, oh.b1, oh.b2, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,             \
+                           (const float *)w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc, nb_apply, loss_out); \
+    })
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
     if (which == 1)         // the row pass's loss partials, folded: any later reader finds them whatever grid it assumes
@@ -3832,88 +3776,10 @@ static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glo
     return (int)hipGetLastError();
 }
 
-// Whether an Adam step takes the one-launch form (tagged_adam_kernel): twinned tables (glove_tables.R_tag / C_tag are the
-// sign; the tags themselves stay zero), a plan with chunk records and id bitmaps, a small batch that touches a minority of the rows
-static bool adam_one_launch(const glove_plan *p, const glove_tables *t, const glove_hyper *h)
-{
-    if (!p || !t || !h || sides_of(h) != 3) return false;
-    if (!t->R_tag || !t->C_tag || !p->r_crec || !p->c_crec || !p->r_mark || !p->c_mark) return false;
-    if (h->step_form != GLOVE_STEP_AUTO && h->step_form != GLOVE_STEP_TAGGED) return false;
-    if (h->step_form == GLOVE_STEP_AUTO && p->host_counts[4] > 0) return false;     // heavy ids: as pick_step_form
-    return p->B <= 2048 && 2 * p->B <= (int64_t)v_row(t) + t->V;
-}
-
-// n consecutive one-launch Adam steps: chain records in the workspace as launch_tagged_chain keeps them, one epilogue per chain
-static int launch_adam_chain(const glove_plan *const *plans, int n, const glove_tables *t, const glove_hyper *h, void *ws,
-                             size_t ws_bytes, float *loss_out, void *stream)
-{
-    if (!plans || n < 1 || !t || !h || !ws) return GLOVE_E_BADARG;
-    const int d4 = t->d / 4;
-    int most_blocks = 1;
-    for (int i = 0; i < n; ++i) {
-        const glove_plan *p = plans[i];
-        if (int rc = check_common(p, t, h, ws)) return rc;
-        if (!adam_one_launch(p, t, h)) return GLOVE_E_BADARG;
-        const int rb = rowpass_blocks(p, pass_shape(d4).lpr);
-        most_blocks = rb > most_blocks ? rb : most_blocks;
-    }
-    if (!t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc || !t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc) return GLOVE_E_BADARG;
-    if (!(h->beta1 > 0.0 && h->beta1 < 1.0 && h->beta2 > 0.0 && h->beta2 < 1.0)) return GLOVE_E_BADARG;
-    const size_t rec_floats = (size_t)kChainHead + (size_t)kPartials * most_blocks;
-    const size_t fit = ws_bytes / (rec_floats * sizeof(float));
-    if (fit < 1) return GLOVE_E_WORKSPACE;
-    const RowShape shape = pass_shape(d4);
-    const int Vr = v_row(t);
-    const StepConsts kc = make_consts(t, h);
-    const float b1 = (float)h->beta1, b2 = (float)h->beta2;
-    const double ln_b1 = log((double)b1), ln_b2 = log((double)b2);
-    hipStream_t st = (hipStream_t)stream;
-    float *recs = (float *)ws;
-    // the sweep's part of the grid: as adam_fused_kernel's; a multiple of 8 workgroups in front of it, so that every step's sweep
-    // finds the rows it wrote last step in the same L2s
-    const int sweep_rows = tagged_sweep_rows(shape.nv);
-    const int sweep_blocks = blocks_for(((int64_t)Vr + t->V + sweep_rows - 1) / sweep_rows, kBlock / shape.lpr);
-    for (int i0 = 0; i0 < n; i0 += (int)fit) {
-        const int m = n - i0 < (int)fit ? n - i0 : (int)fit;
-        int prev_blocks = 0;
-        for (int i = 0; i < m; ++i) {
-            const glove_plan *p = plans[i0 + i];
-            const int row_blocks = rowpass_blocks(p, shape.lpr), chunk_blocks = (2 * row_blocks + 7) & ~7;
-            const int nb = chunk_blocks + sweep_blocks;
-            AdamSide rs, cs;
-            rs.crec = p->r_crec; rs.own = t->R; rs.own_bias = t->br; rs.other = t->C; rs.other_bias = t->bc;
-            rs.S1 = t->s1_R; rs.S1b = t->s1_br; rs.S2 = t->s2_R; rs.S2b = t->s2_br; rs.mark = p->r_mark; rs.own_twin = Vr; rs.other_twin = t->V;
-            rs.n_host = p->host_counts[0]; rs.count_index = 0; rs.capP = rec_cap(p->chunk_cap);
-            cs.crec = p->c_crec; cs.own = t->C; cs.own_bias = t->bc; cs.other = t->R; cs.other_bias = t->br;
-            cs.S1 = t->s1_C; cs.S1b = t->s1_bc; cs.S2 = t->s2_C; cs.S2b = t->s2_bc; cs.mark = p->c_mark; cs.own_twin = t->V; cs.other_twin = Vr;
-            cs.n_host = p->host_counts[2]; cs.count_index = 2; cs.capP = rs.capP;
-            rs.cap_chunks = cs.cap_chunks = p->cap_chunks > 0 ? p->cap_chunks : 1;
-            const float *prev = i > 0 ? recs + (size_t)(i - 1) * rec_floats : nullptr;
-            float *mine = recs + (size_t)i * rec_floats;
-#define CALL(LPR, NV)                                                                                                           \
-            if (LPR * NV == d4)                                                                                                 \
-                hipLaunchKernelGGL((tagged_adam_kernel<LPR, NV, true>), dim3(nb), dim3(kBlock), 0, st, p->counts, rs, cs, row_blocks, \
-                                   chunk_blocks, (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head, \
-                                   h->neg_factor, kc, b1, b2, ln_b1, ln_b2, prev, prev_blocks, mine, i);                        \
-            else                                                                                                                \
-                hipLaunchKernelGGL((tagged_adam_kernel<LPR, NV, false>), dim3(nb), dim3(kBlock), 0, st, p->counts, rs, cs, row_blocks, \
-                                   chunk_blocks, (const float *)t->scalars, (const int64_t *)t->step, d4, h->inv_batch, (int)h->head, \
-                                   h->neg_factor, kc, b1, b2, ln_b1, ln_b2, prev, prev_blocks, mine, i)
-            GLOVE_DISPATCH_PASS_SHAPE(shape, CALL);
-#undef CALL
-            prev_blocks = row_blocks;
-        }
-        hipLaunchKernelGGL(tagged_adam_flush_kernel, dim3(1), dim3(kBlock), 0, st, t->scalars, t->step,
-                           (const float *)(recs + (size_t)(m - 1) * rec_floats), prev_blocks, m, kc, b1, b2, ln_b1, ln_b2,
-                           i0 + m == n ? loss_out : nullptr);
-    }
-    return (int)hipGetLastError();
-}
-
 int glove_step_adam_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                         float *G_flat, float *loss_out, void *stream)
 {
-    if (adam_one_launch(p, t, h)) return launch_adam_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream);
+    if (adam_one_launch(p, t, h)) return launch_tagged_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAM);
     // a batch that touches a minority of the rows (the reference's 1,024 pairs): two launches, no gradient buffer
     // traffic; a batch that touches most rows: the dense form, whose sweep then wastes nothing
     if (int rc = plain_table(t, stream)) return rc;
@@ -3924,6 +3790,36 @@ int glove_step_adam_f32(const glove_plan *p, const glove_tables *t, const glove_
     return glove_dense_adam_f32(t, h, G_flat, loss_out, stream);
 }
 
+// A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl): the passes of `sides`, then apply_sparse_opt_kernel on their ids
+// (1: the row ids alone, no scalar work)
+static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
+                                  int sides, float *loss_out, void *stream)
+{
+    const int opt = h->optimizer;
+    if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL) return GLOVE_E_BADARG;
+    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, sides)) return rc;
+    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
+    hipStream_t st = (hipStream_t)stream;
+    const int d4 = t->d / 4;
+    const RowShape shape = pick_row_shape(d4);
+    IdWork wk = id_work(p);
+    wk.sides = sides;
+    const int nb = apply_blocks(p, shape);
+    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
+    const StepConsts k = make_consts(t, h);
+    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
+    const OptHyper oh = opt_consts(h);
+#define CALL(LPR, NV)                                                                                                      \
+    dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL>(opt, [&](auto o_) {                  \
+        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, \
+                           slot_two(t), d4, k, oh.o, oh.ln_b1, (const int64_t *)t->step, t->scalars,                      \
+                           (const float *)w.blockpart, nb_row, loss_out);                                                 \
+    })
+    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+#undef CALL
+    return (int)hipGetLastError();
+}
+
 int glove_step_sparse_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                           float *G_flat, float *loss_out, void *stream)
 {
@@ -3932,13 +3828,14 @@ int glove_step_sparse_f32(const glove_plan *p, const glove_tables *t, const glov
     if (h->optimizer == GLOVE_OPT_ADAM) return glove_step_adam_f32(p, t, h, ws, ws_bytes, G_flat, loss_out, stream);
     if (int rc = plain_table(t, stream)) return rc;
     if (int rc = check_common(p, t, h, ws)) return rc;
-    if (sides_of(h) != 3 || !t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc) return GLOVE_E_BADARG;
+    if (sides_of(h) != 3) return GLOVE_E_BADARG;
+    if (int rc = check_optimizer(t, h, 3, h->optimizer)) return rc;
     if (h->optimizer == GLOVE_OPT_NADAM)        // passes (marking the batch's ids) + one kernel: apply for the ids, decay of m and v for all other rows
         return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, loss_out, stream, true);
     hipStream_t st = (hipStream_t)stream;
     const StepConsts k = make_consts(t, h);
     if (h->optimizer == GLOVE_OPT_RMSPROP) {
-        if (!G_flat || !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+        if (!G_flat) return GLOVE_E_BADARG;
         if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3)) return rc;
         if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
         DenseSegs segs; float *tail; int nbx, sides;
@@ -3946,35 +3843,7 @@ int glove_step_sparse_f32(const glove_plan *p, const glove_tables *t, const glov
         hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, h->rho, t->scalars, tail, loss_out, 1);
         return (int)hipGetLastError();
     }
-    const bool two_slots = h->optimizer == GLOVE_OPT_ADAMAX || h->optimizer == GLOVE_OPT_ADADELTA || h->optimizer == GLOVE_OPT_FTRL;
-    if (h->optimizer != GLOVE_OPT_SGD && !two_slots) return GLOVE_E_BADARG;
-    if (two_slots && (!t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)) return GLOVE_E_BADARG;
-    if (h->optimizer == GLOVE_OPT_ADAMAX && (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0))) return GLOVE_E_BADARG;
-    if (h->optimizer == GLOVE_OPT_ADADELTA && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
-    if (h->optimizer == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
-    if (h->optimizer == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    IdWork wk = id_work(p);
-    const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
-    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    const OptConsts o = {h->learning_rate, h->epsilon, h->momentum, 0.f, (float)h->beta1, (float)h->beta2, h->nesterov ? 1 : 0, h->rho};
-    const double ln_b1 = h->optimizer == GLOVE_OPT_ADAMAX ? log((double)(float)h->beta1) : 0.0;
-#define LAUNCH_OPT(LPR, NV, OPT)                                                                                           \
-        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, OPT>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
-                           t->s2_br, t->s2_bc, d4, k, o, ln_b1, (const int64_t *)t->step, t->scalars, (const float *)w.blockpart, nb_row, loss_out)
-#define CALL(LPR, NV)                                                                                                       \
-    if (h->optimizer == GLOVE_OPT_SGD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_SGD);                                                  \
-    else if (h->optimizer == GLOVE_OPT_ADAMAX) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAMAX);                                       \
-    else if (h->optimizer == GLOVE_OPT_ADADELTA) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADADELTA);                                   \
-    else LAUNCH_OPT(LPR, NV, GLOVE_OPT_FTRL)
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
-#undef CALL
-#undef LAUNCH_OPT
-    return (int)hipGetLastError();
+    return launch_sparse_opt_step(p, t, h, ws, ws_bytes, 3, loss_out, stream);
 }
 
 int glove_rowside_step_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
@@ -3991,14 +3860,13 @@ int glove_rowside_step_f32(const glove_plan *p, const glove_tables *t, const glo
         return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, nullptr, stream, opt == GLOVE_OPT_NADAM, 1);
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
     if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
+    if (int rc = check_optimizer(t, h, 1, opt)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
     const StepConsts k = make_consts(t, h);
-    const int nb_row = rowpass_blocks(p, pass_shape(d4).lpr);
+    const int nb_row = rowpass_blocks(p, pick_pass_shape(t->d / 4).lpr);
     if (opt == GLOVE_OPT_RMSPROP) {
         // the row half of glove_step_sparse_f32's RMSprop: the summed row gradients into G_flat, the sweep over R's rms slot
-        if (!G_flat || !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
+        if (!G_flat) return GLOVE_E_BADARG;
         if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
         if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
         DenseSegs segs; float *tail; int nbx, sides;
@@ -4006,31 +3874,7 @@ int glove_rowside_step_f32(const glove_plan *p, const glove_tables *t, const glo
         hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, h->rho, t->scalars, tail, nullptr, 0);
     } else {
         // the per-row optimizers: the row pass, then their epilogue on the row ids (apply_sparse_opt_kernel, sides 1: no scalar work)
-        const bool two_slots = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL;
-        if (opt != GLOVE_OPT_SGD && !two_slots) return GLOVE_E_BADARG;
-        if (two_slots && (!t->s2_R || !t->s2_br)) return GLOVE_E_BADARG;
-        if (opt == GLOVE_OPT_ADAMAX && (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0))) return GLOVE_E_BADARG;
-        if (opt == GLOVE_OPT_ADADELTA && !(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
-        if (opt == GLOVE_OPT_FTRL && !(h->learning_rate > 0.f)) return GLOVE_E_BADARG;
-        if (opt == GLOVE_OPT_SGD && !(h->momentum >= 0.f && h->momentum < 1.f)) return GLOVE_E_BADARG;
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
-        IdWork wk = id_work(p);
-        wk.sides = 1;
-        const int nb = wk.heavy_blocks + blocks_for(2 * (int64_t)p->cap_uniq, kBlock / shape.lpr) + 1;
-        const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-        const OptConsts o = {h->learning_rate, h->epsilon, h->momentum, 0.f, (float)h->beta1, (float)h->beta2, h->nesterov ? 1 : 0, h->rho};
-        const double ln_b1 = opt == GLOVE_OPT_ADAMAX ? log((double)(float)h->beta1) : 0.0;
-#define LAUNCH_OPT(LPR, NV, OPT)                                                                                           \
-        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, OPT>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, t->s2_R, t->s2_C, \
-                           t->s2_br, t->s2_bc, d4, k, o, ln_b1, (const int64_t *)t->step, t->scalars, (const float *)w.blockpart, nb_row, nullptr)
-#define CALL(LPR, NV)                                                                                                       \
-        if (opt == GLOVE_OPT_SGD) LAUNCH_OPT(LPR, NV, GLOVE_OPT_SGD);                                                      \
-        else if (opt == GLOVE_OPT_ADAMAX) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADAMAX);                                           \
-        else if (opt == GLOVE_OPT_ADADELTA) LAUNCH_OPT(LPR, NV, GLOVE_OPT_ADADELTA);                                       \
-        else LAUNCH_OPT(LPR, NV, GLOVE_OPT_FTRL)
-        GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
-#undef CALL
-#undef LAUNCH_OPT
+        if (int rc = launch_sparse_opt_step(p, t, h, ws, ws_bytes, 1, nullptr, stream)) return rc;
     }
     // the row pass's loss partials, folded: glove_loss_partials_f32 / the col side's dense gradient find them whatever grid they assume
     hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, st, w.blockpart, nb_row);
@@ -4046,7 +3890,7 @@ int glove_steps_adam_f32(const glove_plan *const *plans, int32_t n, const glove_
         int32_t k = i;
         while (k < n && adam_one_launch(plans[k], t, h)) ++k;
         if (k > i) {
-            if (int rc = launch_adam_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream)) return rc;
+            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream, GLOVE_OPT_ADAM)) return rc;
             i = k;
             continue;
         }
