@@ -77,6 +77,10 @@ FLAGS = (
     Flag("shard-cols", None, False, "with --row-sharded: shard the col table as well (rows and cols on id % ranks; a step fetches "
                                     "the col rows its batch touches from their owners and returns their gradients: two "
                                     "all-to-alls whose size follows the batch, not the vocabulary); --epoch-shuffle full only"),
+    Flag("shard-balance", str, "modulo", "with --row-sharded: which ids a rank owns.  modulo: id % ranks (the vocabulary is sorted "
+                                         "by count, so the first rank owns the heaviest id of every residue class and receives the "
+                                         "most nonzeros); frequency: the ids are renumbered at load so that the ranks receive equal "
+                                         "shares of the nonzeros (trainer.owner_map); checkpoints and exports stay in vocabulary order"),
     Flag("step-form", int, 0, "form of the single-GPU sparse Adagrad step (glove_hyper.step_form): 0 the library chooses, "
                               "1 two launches, 2 / 3 fused forms, 4 fused on a twinned row table"),
     Flag("exchange", str, "auto", "multi-GPU gradient exchange: dense (all-reduce of the [V,d] gradient buffer), rows "
@@ -127,7 +131,22 @@ def init_params(params: dict, write: bool = True) -> dict:
     return params
 
 
+SHARD_BALANCE = ("modulo", "frequency")
+
+
+def check_shard_balance(params: dict) -> None:
+    """--shard-balance names an ownership of the sharded forms: `frequency` alone is refused the way --shard-cols alone is
+    (here before a job directory is made, and by the Estimator for params that did not come from the command line)."""
+    balance = params.get("shard_balance", "modulo")
+    if balance not in SHARD_BALANCE:
+        raise ValueError("--shard-balance must be one of %s, got %r" % (", ".join(SHARD_BALANCE), balance))
+    if balance == "frequency" and not params.get("row_sharded"):
+        raise ValueError("--shard-balance frequency goes with --row-sharded")
+
+
 def parse_args(argv=None) -> dict:
     namespace = build_parser().parse_args(argv)
     logger.info("command line: %s", " ".join(sys.argv if argv is None else argv))
-    return init_params(vars(namespace).copy())
+    params = vars(namespace).copy()
+    check_shard_balance(params)
+    return init_params(params)

@@ -111,13 +111,16 @@ class NonzeroStream:
     """
 
     def __init__(self, coo: dict, batch_size: int, V: int, backend, device, rank=0, world=1, seed=None,
-                 chunk_cap=0, static_plans=True, route=None, cols_by_owner=0, presharded=False):
+                 chunk_cap=0, static_plans=True, route=None, cols_by_owner=0, presharded=False, relabel=None):
         """`static_plans=False`: no index is built here; the caller re-permutes the pairs every epoch
         (`reshuffle_in_place`) and indexes each batch when it is used (--epoch-shuffle full).
         `cols_by_owner` = W > 0 (both tables sharded over W ranks): col ids are renumbered owner-major — id v becomes
         (v % W) * ceil(V / W) + v // W — so that ascending col order IS the order in which a batch's col rows are fetched
         from their owners (owner after owner, local index ascending): a dealt batch then arrives sorted for the sharded step
-        as well (`col_per` = ceil(V / W), `V_cols` = W * col_per: the range of the renumbered ids)."""
+        as well (`col_per` = ceil(V / W), `V_cols` = W * col_per: the range of the renumbered ids).
+        `relabel`: int64[V], a bijection of the vocabulary (trainer.owner_map.balanced_relabel): row and col ids are clamped
+        (an id outside the vocabulary is the unknown token, id 0) and renamed relabel[id] before they are routed and before the
+        owner-major renumbering; whoever holds the tables holds them in the renamed order (relabel[0] need not be 0)."""
         self.B, self.V, self.backend, self.device = int(batch_size), int(V), backend, torch.device(device)
         self.chunk_cap = chunk_cap
         self.gen = torch.Generator(device="cpu")
@@ -136,6 +139,15 @@ class NonzeroStream:
                 return a[mine.to(a.device)].to(self.device)
             return torch.from_numpy(np.ascontiguousarray(a))[mine].to(self.device)
         self.row, self.col, self.w, self.y = take(coo["row"]), take(coo["col"]), take(coo["w"]), take(coo["y"])
+        if relabel is not None:
+            names = torch.as_tensor(relabel, dtype=torch.int64).to(self.device)
+            if names.numel() != self.V:
+                raise ValueError("relabel names %d ids, the vocabulary has %d" % (names.numel(), self.V))
+
+            def rename(ids):
+                i = ids.long()
+                return names[torch.where((i < 0) | (i >= self.V), torch.zeros_like(i), i)].to(ids.dtype)
+            self.row, self.col = rename(self.row), rename(self.col)
         if route is not None:
             # row-sharded model: every nonzero moves to the rank that owns its row (one all-to-all at load), row ids
             # become local.  Every rank keeps ALL it received: the stream is endless (data_utils.py:12-21 num_epochs=None),
@@ -150,10 +162,18 @@ class NonzeroStream:
             dist.all_reduce(have, op=dist.ReduceOp.MAX)
             most, least = int(have[0].item()), -int(have[1].item())
             self.load_imbalance = most / max(least, 1)
+            col_side = ""
+            if relabel is not None:
+                # the col side of the same numbering: how many of the stream's col ids each rank owns — what it serves when
+                # the col table is sharded too (exchange volume only: the epoch length follows the row side)
+                served = torch.bincount(self.col.long() % world, minlength=world)
+                dist.all_reduce(served)
+                self.col_imbalance = int(served.max().item()) / max(int(served.min().item()), 1)
+                col_side = "; col ids by owner, most / least = %.2fx" % self.col_imbalance
             (logger.warning if self.load_imbalance > 1.5 else logger.info)(
                 "row-sharded stream: %d nonzeros on this rank, most / least over the ranks = %d / %d (%.2fx): "
-                "the nonzeros of the lighter ranks are revisited that much more often", self.row.numel(), most, least,
-                self.load_imbalance)
+                "the nonzeros of the lighter ranks are revisited that much more often%s", self.row.numel(), most, least,
+                self.load_imbalance, col_side)
         self.col_per, self.V_cols = 0, self.V
         if cols_by_owner:
             W = int(cols_by_owner)

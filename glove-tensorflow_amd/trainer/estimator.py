@@ -17,7 +17,7 @@ import time
 
 import torch
 
-from trainer.config_utils import parse_args
+from trainer.config_utils import check_shard_balance, parse_args
 from trainer.data_utils import NonzeroStream, file_lines, get_id_string_table, load_interaction_csv
 from trainer.model_utils import MatrixFactorisation, get_predictions, logged_biases, summary_histograms, summary_values
 from trainer.stepper import HipBackend, Stepper
@@ -76,21 +76,33 @@ class Estimator:
         self.both_sharded = self.row_sharded and bool(params.get("shard_cols"))
         if params.get("shard_cols") and not params.get("row_sharded"):
             raise ValueError("--shard-cols goes with --row-sharded")
+        check_shard_balance(params)
+        # --shard-balance frequency: the vocabulary is renumbered so that the ranks receive equal shares of the nonzeros
+        # (trainer.owner_map); ownership stays id % ranks of the NEW ids.  The map is a function of the data alone: every rank
+        # computes it here, from the row histogram of the whole file, before the tables are cut; nothing of it is stored
+        self.relabel, self._coo = None, None
+        if params.get("shard_balance", "modulo") == "frequency":
+            if self.row_sharded:
+                self.relabel = self._balanced_relabel()
+            else:
+                logger.info("--shard-balance frequency: one rank, nothing is sharded: the flag does nothing here")
         if self.row_sharded:
             # keep this rank's rows (u % world == rank) of the row side; the col side stays replicated, or is cut the same way
+            # (the whole tables were drawn in vocabulary order: with an id map they are cut through it, the replicated col
+            # side included — token u sits in row relabel[u] of every table)
             from trainer.hip_api import DeviceTables
             from trainer.stepper import owned_rows
             whole = self.model.tables
             mine = owned_rows(whole.V, self.world, self.rank)
             shard = DeviceTables(whole.V, whole.d_model, whole.optimizer, device=self.device, seed=0,
                                  V_row=mine, V_col=mine if self.both_sharded else None)
-            shard.load_whole_state_dict(whole.state_dict(), self.world, self.rank)
+            shard.load_whole_state_dict(whole.state_dict(), self.world, self.rank, relabel=self.relabel)
             self.model.tables = shard
             if hasattr(self.backend, "shard_rows"):
                 self.backend.shard_rows = shard.V_row        # the routed stream carries shard-local row ids
         self.ckpt = CheckpointManager(params["job_dir"], params.get("save_checkpoints_secs", 300.0),
                                       params.get("keep_checkpoint_max", 5))
-        self.ckpt.restore(self.model.tables, shard=(self.world, self.rank) if self.row_sharded else None)
+        self.ckpt.restore(self.model.tables, shard=(self.world, self.rank) if self.row_sharded else None, relabel=self.relabel)
         self._stream = None
         self._events = {}
         self.reshuffling = params.get("epoch_shuffle", "full") == "full"
@@ -99,18 +111,37 @@ class Estimator:
         self.logistic = params.get("head", "regression") == "logistic"
 
     # ---- input_fn
+    def _load_coo(self) -> dict:
+        """The parsed CSV (every rank parses the whole file before it takes its slice); kept until the stream has it."""
+        if self._coo is None:
+            a = self.params["input_fn_args"]
+            row, col, weight, target = a["select_columns"]
+            self._coo = load_interaction_csv(a["file_pattern"], self.params["vocab_txt"], row, col, weight, target,
+                                             cache_dir=self.params["job_dir"] if self.rank == 0 else None)
+        return self._coo
+
+    def _balanced_relabel(self) -> torch.Tensor:
+        from trainer import owner_map
+        coo = self._load_coo()
+        counts = owner_map.id_histogram(coo["row"], self.vocab_size)         # the whole file's: the same array on every rank
+        perm = owner_map.balanced_relabel(counts, self.world)
+        cols = owner_map.id_histogram(coo["col"], self.vocab_size)
+        ratio = lambda c, p: owner_map.imbalance(owner_map.shard_loads(c, p, self.world))
+        logger.info("--shard-balance frequency over %d ranks: nonzeros by row owner, most / least = %.4fx (id %% ranks: %.4fx); "
+                    "by col owner %.4fx (%.4fx)", self.world, ratio(counts, perm), ratio(counts, None), ratio(cols, perm),
+                    ratio(cols, None))
+        return torch.from_numpy(perm)
+
     def stream(self) -> NonzeroStream:
         if self._stream is None:
             a = self.params["input_fn_args"]
-            row, col, weight, target = a["select_columns"]
-            coo = load_interaction_csv(a["file_pattern"], self.params["vocab_txt"], row, col, weight, target,
-                                       cache_dir=self.params["job_dir"] if self.rank == 0 else None)
+            coo, self._coo = self._load_coo(), None
             self._stream = NonzeroStream(coo, a["batch_size"], self.vocab_size, self.backend, self.device,
                                          rank=self.rank, world=self.world, seed=self.params.get("seed"),
                                          chunk_cap=self.params.get("chunk_cap", 0),
                                          static_plans=not self.reshuffling,
                                          route=self.dist if self.row_sharded else None,
-                                         cols_by_owner=self.world if self.both_sharded else 0)
+                                         cols_by_owner=self.world if self.both_sharded else 0, relabel=self.relabel)
         return self._stream
 
     def _log(self, name, record, histograms=None):
@@ -344,7 +375,7 @@ class Estimator:
     def _save_checkpoint(self):
         """Rank 0 writes; a row-sharded run first gathers the whole model (collective: every rank calls this)."""
         tables = self.model.tables
-        state = tables.gathered_state_dict(self.dist, self.world) if self.row_sharded else None
+        state = tables.gathered_state_dict(self.dist, self.world, relabel=self.relabel) if self.row_sharded else None
         if self.rank == 0:
             self.ckpt.save(tables, state=state)
 
@@ -391,13 +422,27 @@ class Estimator:
         return rec
 
     # ---- PREDICT
+    def _vocabulary_order_model(self):
+        """What PREDICT addresses by vocabulary id: the model itself, or — a sharded run — the whole row table gathered from
+        the ranks (collective) and put back into vocabulary order through the id map."""
+        if not self.row_sharded:
+            return self.model
+        from types import SimpleNamespace
+        t = self.model.tables
+        R = t.gather_whole(t.R, self.dist, self.world)
+        if self.relabel is not None:
+            R = R[self.relabel.to(R.device)]
+        R = R.contiguous()
+        return SimpleNamespace(tables=SimpleNamespace(R=R, embeddings=lambda name: R[:, :t.d_model]))
+
     def predict(self, batch=256):
         """Every vocab line as the query token (estimator.py:59-76); yields one dict per token."""
         id_string = get_id_string_table(self.params["vocab_txt"])
         k = min(self.params.get("top_k", 20), self.vocab_size)
+        model = self._vocabulary_order_model()
         for s in range(0, self.vocab_size, batch):
             ids = torch.arange(s, min(s + batch, self.vocab_size), dtype=torch.int32)
-            out = get_predictions(self.backend, self.model, ids, id_string, k)
+            out = get_predictions(self.backend, model, ids, id_string, k)
             for i in range(len(ids)):
                 yield {"input_string": out["input_string"][i], "input_embedding": out["input_embedding"][i].numpy(),
                        "top_k_similarity": out["top_k_similarity"][i].numpy(),

@@ -481,29 +481,49 @@ class DeviceTables:
         dist.all_gather(parts, pad)
         return torch.cat(parts, 0)
 
-    def gathered_state_dict(self, dist, world: int) -> dict:
+    def gathered_state_dict(self, dist, world: int, relabel=None) -> dict:
         """state_dict() of the WHOLE model: the shards of all ranks (the row side; the col side too when it is sharded) are
         all-gathered and interleaved back into [V, ...] arrays, so the checkpoint has the same format as an unsharded
-        run's (collective)."""
+        run's (collective).
+        `relabel`: int64[V], the bijection the run's ids were renamed by (trainer.owner_map): row relabel[u] of every table
+        here — sharded or replicated — is token u; the dict comes out in vocabulary order (row u is token u), as it always is."""
         out = self.state_dict()
         out["V_row"] = self.V
-        for n in self._sharded_names():
-            out[n] = self._logical(self.gather_whole(getattr(self, n), dist, world))
-            out["slot1_" + n] = self._logical(self.gather_whole(self.s1[n], dist, world))
-            if n in self.s2:
-                out["slot2_" + n] = self._logical(self.gather_whole(self.s2[n], dist, world))
+        sharded = self._sharded_names()
+        names = None if relabel is None else self._relabel_index(relabel)
+        for n in (sharded if names is None else self.NAMES):
+            for key, x in ((n, getattr(self, n)), ("slot1_" + n, self.s1[n]), ("slot2_" + n, self.s2.get(n))):
+                if x is None:
+                    continue
+                whole = self._logical(self.gather_whole(x, dist, world) if n in sharded else x)
+                out[key] = whole if names is None else whole[names]
         return out
 
-    def load_whole_state_dict(self, sd: dict, world: int, rank: int):
-        """Takes this rank's rows out of a whole-model state dict (the inverse of gathered_state_dict)."""
+    def load_whole_state_dict(self, sd: dict, world: int, rank: int, relabel=None):
+        """Takes this rank's rows out of a whole-model state dict (the inverse of gathered_state_dict).
+        `relabel`: the bijection this run's ids are renamed by: token u goes to row relabel[u] of every table, and the shard
+        is cut from that order."""
         if sd.get("V_row", sd["V"]) != sd["V"]:
             raise ValueError("the checkpoint holds a row shard, not the whole model")
         mine = dict(sd, V_row=self.V_row)
-        for n in self._sharded_names():
+        sharded = self._sharded_names()
+        tokens = None
+        if relabel is not None:
+            names = self._relabel_index(relabel)
+            tokens = torch.empty_like(names)
+            tokens[names] = torch.arange(self.V, dtype=torch.int64)        # row p holds token tokens[p]
+        for n in (sharded if tokens is None else self.NAMES):
             for key in (n, "slot1_" + n, "slot2_" + n):
                 if key in sd:
-                    mine[key] = sd[key][rank::world]
+                    whole = sd[key] if tokens is None else sd[key][tokens]
+                    mine[key] = whole[rank::world] if n in sharded else whole
         self.load_state_dict(mine)
+
+    def _relabel_index(self, relabel) -> torch.Tensor:
+        names = torch.as_tensor(relabel, dtype=torch.int64).cpu()
+        if names.numel() != self.V:
+            raise ValueError("relabel names %d ids, the vocabulary has %d" % (names.numel(), self.V))
+        return names
 
     @property
     def global_bias(self) -> float:

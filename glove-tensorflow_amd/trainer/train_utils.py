@@ -76,7 +76,8 @@ class CheckpointManager:
 
     def save(self, tables, extra=None, state=None) -> str:
         """`state`: the state dict to store instead of tables.state_dict() (a row-sharded run hands over the
-        gathered whole-model dict, so the file looks like any other checkpoint)."""
+        gathered whole-model dict — DeviceTables.gathered_state_dict, given the run's id map when it has one —, so
+        the file looks like any other checkpoint: vocabulary order, nothing about the sharding in it)."""
         step = tables.global_step
         name = "%s%d" % (self.PREFIX, step)
         os.makedirs(self.model_dir, exist_ok=True)
@@ -99,16 +100,19 @@ class CheckpointManager:
         logger.info("saved checkpoint %s", name)
         return name
 
-    def restore(self, tables, shard=None) -> bool:
+    def restore(self, tables, shard=None, relabel=None) -> bool:
         """`shard = (world, rank)`: the tables hold one rank's rows of a row-sharded run; checkpoints always hold
-        the whole model."""
+        the whole model, in vocabulary order.  `relabel`: the id map of this run (--shard-balance frequency,
+        trainer.owner_map), recomputed from the data at load: the rows are cut through it."""
         f = self.latest()
         if f is None:
             return False
         blob = torch.load(f, map_location="cpu", weights_only=False)
         if shard is None:
+            if relabel is not None:
+                raise ValueError("an id map belongs to a sharded run: pass shard=(world, rank) with it")
             tables.load_state_dict(blob["tables"])
         else:
-            tables.load_whole_state_dict(blob["tables"], *shard)
+            tables.load_whole_state_dict(blob["tables"], *shard, relabel=relabel)
         logger.info("restored %s (global_step %d)", f, tables.global_step)
         return True
