@@ -1394,12 +1394,12 @@ __device__ inline void nadam_elem(float &w, float &m, float &v, float g, const N
     w -= k.lr * m_bar / (sqrtf(v / k.v_den) + k.eps);
 }
 
-// ---- the element updates of the per-row Keras optimizers (SGD, Adamax, Adadelta, Ftrl): include/glove_hip.h glove_hyper.optimizer;
+// ---- the element updates of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam): include/glove_hip.h glove_hyper.optimizer;
 // used by the apply epilogues of the single-GPU step (SparseOptApply) and of the touched-rows exchange (apply_packed_kernel)
 struct OptConsts { float lr, eps, momentum, lr_t, b1, b2; int nesterov; float rho; };
 template <int OPT> struct OptSlots {
     static constexpr bool two = OPT == GLOVE_OPT_ADAMAX || OPT == GLOVE_OPT_ADADELTA || OPT == GLOVE_OPT_FTRL || OPT == GLOVE_OPT_NADAM ||
-                                OPT == GLOVE_OPT_ADAM;
+                                OPT == GLOVE_OPT_ADAM || OPT == GLOVE_OPT_LAZYADAM;
 };
 template <int OPT>
 struct OptElem {
@@ -1443,7 +1443,8 @@ struct OptElem {
         if (g != 0.f) w -= o.lr * g / (sqrtf(a) + o.eps);
     }
     // (nk: Nadam's constants of this step — the touched-rows exchange only: apply_packed_kernel; a = m, b = v.  Adam: a = m,
-    // b = v, o.lr_t of this step — the touched-rows exchange only, the rows no list names take the sweep's G = 0 update)
+    // b = v, o.lr_t of this step — the touched-rows exchange only, the rows no list names take the sweep's G = 0 update.
+    // LazyAdam: Adam's element update on the touched rows alone, no sweep anywhere: every other row keeps its bits)
     __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o, const NadamConsts &nk)
     {
         if (OPT == GLOVE_OPT_SGD) sgd(w, a, g, o);
@@ -1451,7 +1452,7 @@ struct OptElem {
         else if (OPT == GLOVE_OPT_ADADELTA) adadelta(w, a, b, g, o);
         else if (OPT == GLOVE_OPT_NADAM) nadam_elem(w, a, b, g, nk);
         else if (OPT == GLOVE_OPT_RMSPROP) rmsprop(w, a, g, o);
-        else if (OPT == GLOVE_OPT_ADAM) adam_elem(w, a, b, g, o.lr_t, o.b1, o.b2, o.eps);
+        else if (OPT == GLOVE_OPT_ADAM || OPT == GLOVE_OPT_LAZYADAM) adam_elem(w, a, b, g, o.lr_t, o.b1, o.b2, o.eps);
         else ftrl(w, a, b, g, o);
     }
     __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o) { one(w, a, b, g, o, NadamConsts{}); }
@@ -1462,7 +1463,7 @@ struct OptElem {
 // Instead the group's LPR lanes look LPR entries up at once — lane t the id, side, bias gradient and mark of the t-th
 // of them — and the rows are then moved two entries at a time, what each needs handed round by lane shuffles: one
 // round trip per pair of entries.
-// OPT: GLOVE_OPT_ADAGRAD, or one of the per-row Keras optimizers (OptElem: SGD, Adamax, Adadelta, Ftrl) — only touched rows move
+// OPT: GLOVE_OPT_ADAGRAD, or one of the per-row optimizers (OptElem: SGD, Adamax, Adadelta, Ftrl, LazyAdam) — only touched rows move
 // under all of them, so the exchange is the same and the epilogue differs.  The dense-decay ones (Nadam, Adam, RMSprop) move
 // every row's slots every step: decay_unmarked_kernel gives the rows no list names their G = 0 update first, and the listed
 // rows take the epilogue here.  s2: the second slot of every variable where the optimizer has one (scalars[2] for the global bias).
@@ -1586,7 +1587,8 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
     // t = global_step as the passes of this step left it (Adamax: lr_t = lr / (1 - beta1^t), as apply_sparse_opt_kernel)
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
     // Adam (every row moves: the rows no list names took the G = 0 update in decay_unmarked_kernel, the launch before): lr_t of step t
-    if (OPT == GLOVE_OPT_ADAM) o.lr_t = adam_lr_t(o.lr, ln_beta1, ln_beta2, *step);
+    // (LazyAdam: the same lr_t of the global step, on the listed rows alone — no launch before this one)
+    if (OPT == GLOVE_OPT_ADAM || OPT == GLOVE_OPT_LAZYADAM) o.lr_t = adam_lr_t(o.lr, ln_beta1, ln_beta2, *step);
     // Nadam (the ranks' touched rows move; every other row's m and v have decayed in decay_unmarked_kernel, the launch before):
     // the constants of step t = global_step as the passes left it
     NadamConsts nk = {};
@@ -2501,7 +2503,8 @@ __global__ __launch_bounds__(kBlock) void dense_adam_kernel(
 // ------------------------------------------------------------------------------------------
 // The other Keras optimizers `tf.keras.optimizers.get(name)` resolves (reference src/models/train_utils.py:13-16), as apply
 // epilogues on the same traversal as AdagradApply.  Semantics: include/glove_hip.h glove_hyper.optimizer; restated in
-// oracle/glove_ref.py (_sgd, _rmsprop_dense_decay, _adamax).
+// oracle/glove_ref.py (_sgd, _rmsprop_dense_decay, _adamax).  LazyAdam (GLOVE_OPT_LAZYADAM, this build's addition: Adam's update
+// on the touched rows alone) is the one epilogue here that is no Keras-legacy name; restated in tests/lazyadam_ref.py.
 // ------------------------------------------------------------------------------------------
 template <int LPR, int NV, int OPT>
 struct SparseOptApply {
@@ -2551,11 +2554,13 @@ struct SparseOptApply {
 template <int LPR, int NV, int OPT>
 __global__ __launch_bounds__(kBlock) void apply_sparse_opt_kernel(
     IdWork wk, SideBufs rs, SideBufs cs, SlotTwo s2, int d4, StepConsts k, OptConsts o,
-    double ln_beta1, const int64_t *__restrict__ step, float *__restrict__ scalars, const float *__restrict__ blockpart,
-    int nblocks_rowpass, float *__restrict__ loss_out)
+    double ln_beta1, double ln_beta2, const int64_t *__restrict__ step, float *__restrict__ scalars,
+    const float *__restrict__ blockpart, int nblocks_rowpass, float *__restrict__ loss_out)
 {
-    // t = global_step after rowpass advanced it (Adamax: lr_t = lr / (1 - beta1^t))
+    // t = global_step after rowpass advanced it (Adamax: lr_t = lr / (1 - beta1^t); LazyAdam: Adam's lr_t, bias-corrected by the
+    // global t whenever a row was last touched)
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
+    if (OPT == GLOVE_OPT_LAZYADAM) o.lr_t = adam_lr_t(o.lr, ln_beta1, ln_beta2, *step);
     const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k,
                                                   SparseOptApply<LPR, NV, OPT>{rs, cs, s2, d4, (int)(threadIdx.x % LPR), o});
     if (scalar_duty) {
@@ -2797,7 +2802,7 @@ static OptHyper opt_consts(const glove_hyper *h)
 // there and its hyper-parameters are in range
 static int check_optimizer(const glove_tables *t, const glove_hyper *h, int sides, int opt)
 {
-    const bool betas = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM;
+    const bool betas = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_LAZYADAM;
     const bool two_slots = betas || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL;
     if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && !two_slots) return GLOVE_E_BADARG;
     if ((sides & 1) && (!t->s1_R || !t->s1_br || (two_slots && (!t->s2_R || !t->s2_br)))) return GLOVE_E_BADARG;
@@ -3225,6 +3230,7 @@ int glove_dense_adagrad_f32(const glove_tables *t, const glove_hyper *h, float *
 int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
 {
     DenseSegs segs; float *tail; int nbx, sides;
+    if (h && h->optimizer == GLOVE_OPT_LAZYADAM) return GLOVE_E_BADARG;      // touched rows only: it has no dense sweep
     if (int rc = plain_table(t, stream)) return rc;
     if (h && h->optimizer == GLOVE_OPT_RMSPROP) {
         // the other dense-decay optimizer of the Keras set: its whole rms slot decays every step, entries with a gradient move —
@@ -3468,7 +3474,7 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         const int scal = first == 0 ? do_scalars : 0;
 #define CALL(LPR, NV)                                                                                                         \
         dispatch_opt<GLOVE_OPT_ADAGRAD, GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_NADAM, GLOVE_OPT_ADAM,  \
-                     GLOVE_OPT_RMSPROP, GLOVE_OPT_FTRL>(opt, [&](auto o_) {                                                   \
+                     GLOVE_OPT_RMSPROP, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM>(opt, [&](auto o_) {                               \
             hipLaunchKernelGGL((apply_packed_kernel<LPR, NV, decltype(o_)::value>), dim3(nbx, pls.n), dim3(kBlock), 0, st, pls, dv, rs, \
                                cs, s2, d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars,    \
                                loss_out, scal);                                                                               \
@@ -3790,13 +3796,14 @@ int glove_step_adam_f32(const glove_plan *p, const glove_tables *t, const glove_
     return glove_dense_adam_f32(t, h, G_flat, loss_out, stream);
 }
 
-// A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl): the passes of `sides`, then apply_sparse_opt_kernel on their ids
+// A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam): the passes of `sides`, then apply_sparse_opt_kernel on their ids
 // (1: the row ids alone, no scalar work)
 static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                                   int sides, float *loss_out, void *stream)
 {
     const int opt = h->optimizer;
-    if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL) return GLOVE_E_BADARG;
+    if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL && opt != GLOVE_OPT_LAZYADAM)
+        return GLOVE_E_BADARG;
     if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, sides)) return rc;
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
     hipStream_t st = (hipStream_t)stream;
@@ -3810,9 +3817,9 @@ static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, co
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
     const OptHyper oh = opt_consts(h);
 #define CALL(LPR, NV)                                                                                                      \
-    dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL>(opt, [&](auto o_) {                  \
+    dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM>(opt, [&](auto o_) { \
         hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, \
-                           slot_two(t), d4, k, oh.o, oh.ln_b1, (const int64_t *)t->step, t->scalars,                      \
+                           slot_two(t), d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,            \
                            (const float *)w.blockpart, nb_row, loss_out);                                                 \
     })
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);

@@ -18,9 +18,10 @@ logger = logging.getLogger(__name__)
 PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
 
-GLOVE_ABI_VERSION = 14
+GLOVE_ABI_VERSION = 15
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
-OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7}      # glove_hyper.optimizer (GLOVE_OPT_*)
+OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7,
+                   "LazyAdam": 8}      # glove_hyper.optimizer (GLOVE_OPT_*); LazyAdam is this build's addition, no Keras-legacy name
 STEP_AUTO, STEP_TWO_LAUNCH, STEP_FUSED_ONE_PASS, STEP_FUSED_THREE_LAUNCH, STEP_FUSED_TWIN, STEP_TAGGED = 0, 1, 2, 3, 4, 5   # glove_hyper.step_form (2: tests / comparisons only)
 TAGGED_STEP_MAX_BATCH = 2048      # GLOVE_STEP_AUTO takes the tagged step up to this batch size on step-tagged tables
 DEFAULT_CHUNK_CAP = 32
@@ -280,9 +281,9 @@ class DeviceTables:
             w = getattr(self, n)
             if optimizer in ("Adagrad", "Ftrl"):
                 self.s1[n] = torch.full_like(w, 0.1)   # initial_accumulator_value (both optimizers' Keras default)
-            else:                                      # Adam m / v, Adamax m / v, Adadelta accum_grad / accum_var; SGD momentum accumulator, RMSprop rms: zeros
+            else:                                      # Adam / LazyAdam m / v, Adamax m / v, Adadelta accum_grad / accum_var; SGD momentum accumulator, RMSprop rms: zeros
                 self.s1[n] = torch.zeros_like(w)
-            if optimizer in ("Adam", "Adamax", "Adadelta", "Ftrl", "Nadam"):
+            if optimizer in ("Adam", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam"):
                 self.s2[n] = torch.zeros_like(w)       # (Ftrl: linear)
         if optimizer in ("Adagrad", "Ftrl"):
             self.scalars[1] = 0.1
@@ -1115,7 +1116,7 @@ class GloveHip:
                "glove_step_adam_f32")
 
     def step_sparse(self, plan, tables, hyper, G_flat=None, loss_out=None, ws=None):
-        """One step under the Keras optimizer `tables.optimizer` names (glove_step_sparse_f32: SGD, RMSprop, Adamax, Adadelta, Ftrl, Nadam; Adagrad
+        """One step under the Keras optimizer `tables.optimizer` names (glove_step_sparse_f32: SGD, RMSprop, Adamax, Adadelta, Ftrl, Nadam, LazyAdam; Adagrad
         and Adam go to their own entry points).  G_flat: the dense gradient buffer RMSprop, Nadam and Adam need."""
         ws = self.step_workspace(plan, tables.d) if ws is None else ws
         hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]

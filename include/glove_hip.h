@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GLOVE_ABI_VERSION 14   /* 14: glove_hyper.sweep_sides; glove_apply_packed_adagrad_f32 takes GLOVE_OPT_ADAM and GLOVE_OPT_RMSPROP and applies the dense-decay optimizers (Adam, RMSprop, Nadam) to one side; glove_dense_adam_f32 applies RMSprop to one side; glove_rowside_step_f32 (the row side of a step under any of the eight optimizers): the sharded multi-GPU forms run every Keras optimizer; 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
+#define GLOVE_ABI_VERSION 15   /* 15: GLOVE_OPT_LAZYADAM (Adam on the touched rows alone, this build's addition) in glove_step_sparse_f32, glove_rowside_step_f32 and glove_apply_packed_adagrad_f32; no entry point added; 14: glove_hyper.sweep_sides; glove_apply_packed_adagrad_f32 takes GLOVE_OPT_ADAM and GLOVE_OPT_RMSPROP and applies the dense-decay optimizers (Adam, RMSprop, Nadam) to one side; glove_dense_adam_f32 applies RMSprop to one side; glove_rowside_step_f32 (the row side of a step under any of the eight optimizers): the sharded multi-GPU forms run every Keras optimizer; 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
 
 #define GLOVE_E_BADARG   (-1)   /* null pointer / non-positive size / d % 4 != 0 */
 #define GLOVE_E_WORKSPACE (-2)  /* workspace or plan storage too small */
@@ -147,7 +147,17 @@ typedef struct glove_hyper {
      *                      odd and even steps) m and v decay over the WHOLE variable and take (1 - beta) G, G^2 on the touched
      *                      rows, which alone move: with u_i = beta1 (1 - 0.5 0.96^(0.004 i)) and P_t = u_1 .. u_t,
      *                      var -= lr ((1 - u_t) G / (1 - P_t) + u_{t+1} m / (1 - P_{t+1})) / (sqrt(v / (1 - beta2^t)) + epsilon).
-     *                      Needs G_flat (its bias segments carry the marks of the batch's ids, as in glove_step_adam_f32) */
+     *                      Needs G_flat (its bias segments carry the marks of the batch's ids, as in glove_step_adam_f32)
+     *   GLOVE_OPT_LAZYADAM (slot1 = m, slot2 = v, zeros; beta1 0.9, beta2 0.999, epsilon 1e-7) NOT a Keras-legacy name and not
+     *                      bit-comparable with GLOVE_OPT_ADAM: Adam that moves only the rows a batch touches (the lazy variant
+     *                      of tfa.optimizers.LazyAdam / torch.optim.SparseAdam).  For each distinct id of the batch, on each
+     *                      side, with G its summed gradient (activity-L2 term included): m = beta1 m + (1 - beta1) G;
+     *                      v = beta2 v + (1 - beta2) G^2; var -= lr_t m / (sqrt(v) + epsilon), with
+     *                      lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) in fp32 by GLOVE_OPT_ADAM's own expression and
+     *                      t = global_step as this step's row pass advanced it — the GLOBAL step even for a row last touched
+     *                      long ago, not a per-row counter.  Rows the batch does not touch keep var, m and v bit for bit.
+     *                      The global bias is a dense variable: it takes the plain Adam update every step (scalars[1],
+     *                      scalars[2]).  No sweep, no marks, no G_flat; never the one-launch or tagged forms */
     int32_t optimizer;
     float momentum;             /* SGD, Keras default 0 */
     int32_t nesterov;           /* SGD, Keras default 0 */
@@ -168,6 +178,7 @@ typedef struct glove_hyper {
 #define GLOVE_OPT_ADADELTA 5
 #define GLOVE_OPT_FTRL 6
 #define GLOVE_OPT_NADAM 7
+#define GLOVE_OPT_LAZYADAM 8
 
 #define GLOVE_HEAD_REGRESSION 0
 #define GLOVE_HEAD_LOGISTIC 1
@@ -416,8 +427,8 @@ int glove_count_packed_f32(const glove_packed_list *lists, int32_t n_lists, cons
  * zeroing.  capacity_entries bounds the entry count of a list whose count lives in its header. */
 int glove_combine_packed_f32(const glove_packed_list *list, int32_t tag, const glove_tables *t, float *G_flat,
                              int32_t *mark, int64_t capacity_entries, void *stream);
-/* The optimizer glove_hyper.optimizer names — Adagrad, or one of the per-row Keras optimizers (GLOVE_OPT_SGD, _ADAMAX, _ADADELTA,
- * _FTRL: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*), or one
+/* The optimizer glove_hyper.optimizer names — Adagrad, or one of the per-row optimizers (GLOVE_OPT_SGD, _ADAMAX, _ADADELTA,
+ * _FTRL, _LAZYADAM: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*), or one
  * of the dense-decay ones, whose slots move on every row every step: first the rows NO list names on the sides
  * glove_hyper.sweep_sides selects take their G = 0 update (GLOVE_OPT_NADAM: m and v decay; GLOVE_OPT_ADAM: m and v decay and
  * the row moves, lr_t of t = global_step; GLOVE_OPT_RMSPROP: the rms slot decays) — which needs the lists counted into `mark`
@@ -449,7 +460,7 @@ int glove_rowside_step_adagrad_f32(const glove_plan *plan, const glove_tables *t
  * bias, loss and Nadam's momentum cache go with the col side's apply).  Adagrad: glove_rowside_step_adagrad_f32.  Adam, Nadam:
  * the row pass marks the batch's row ids in G_flat, then one kernel applies the row ids and gives every other row of the row
  * table its G = 0 update (m and v decay; Adam: the row moves too), clearing the marks.  RMSprop: the row pass, the summed row
- * gradients into G_flat, the sweep over the row table's rms slot.  SGD, Adamax, Adadelta, Ftrl: the row pass, then their
+ * gradients into G_flat, the sweep over the row table's rms slot.  SGD, Adamax, Adadelta, Ftrl, LazyAdam: the row pass, then their
  * epilogue on the row ids.  t = global_step as this call's row pass advanced it.  G_flat, all zero on entry and on return:
  * Adam, Nadam: V_row floats (the marks); RMSprop: the row half [G_R | G_br] of the glove_dense_grad_layout layout for these
  * tables (the start of a whole dense gradient buffer serves both); unused by Adagrad and the per-row ones.
