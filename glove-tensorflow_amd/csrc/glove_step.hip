@@ -1394,13 +1394,35 @@ __device__ inline void nadam_elem(float &w, float &m, float &v, float g, const N
     w -= k.lr * m_bar / (sqrtf(v / k.v_den) + k.eps);
 }
 
-// ---- the element updates of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam): include/glove_hip.h glove_hyper.optimizer;
-// used by the apply epilogues of the single-GPU step (SparseOptApply) and of the touched-rows exchange (apply_packed_kernel)
+// ---- the element updates of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam, RowWiseAdagrad): include/glove_hip.h
+// glove_hyper.optimizer; used by the apply epilogues of the single-GPU step (SparseOptApply) and of the touched-rows exchange
+// (apply_packed_kernel)
 struct OptConsts { float lr, eps, momentum, lr_t, b1, b2; int nesterov; float rho; };
 template <int OPT> struct OptSlots {
     static constexpr bool two = OPT == GLOVE_OPT_ADAMAX || OPT == GLOVE_OPT_ADADELTA || OPT == GLOVE_OPT_FTRL || OPT == GLOVE_OPT_NADAM ||
                                 OPT == GLOVE_OPT_ADAM || OPT == GLOVE_OPT_LAZYADAM;
+    // RowWiseAdagrad: slot 1 of an embedding table is ONE float per row (float[rows], indexed by id, not by id * d)
+    static constexpr bool row_wise = OPT == GLOVE_OPT_ROWWISE_ADAGRAD;
 };
+
+// RowWiseAdagrad on one embedding row, held by its group of LPR lanes (every lane of the group is here): G is the id's COMPLETE
+// summed gradient (activity-L2 term in; the lanes and columns past the row end hold 0 and add nothing), A the row's one
+// accumulator, the same in every lane on entry and on return.  A += (sum_j G_j^2) / d_model, then W -= lr G / (sqrt(A) + eps)
+// with the incremented A.  The sum has a fixed order (dot4 chains per lane, then the group butterfly) and the rounding sequence
+// is spelled out: both kernels that apply it give the same bits.
+template <int LPR, int NV>
+__device__ inline void rowwise_adagrad_row(f4 (&Wv)[NV], float &A, const f4 (&G)[NV], float lr, float eps, float inv_d)
+{
+#pragma clang fp contract(off)
+    float sq = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < NV; ++kk) sq += dot4(G[kk], G[kk]);
+    sq = group_sum<LPR>(sq);
+    A += sq * inv_d;
+    const float scale = lr * inv_sqrt_eps(A, eps);
+#pragma unroll
+    for (int kk = 0; kk < NV; ++kk) Wv[kk] -= scale * G[kk];
+}
 template <int OPT>
 struct OptElem {
     // Adadelta (kernel SparseApplyAdadelta): a = accum_grad, u = accum_var
@@ -1435,6 +1457,14 @@ struct OptElem {
         v = fmaxf(o.b2 * v, fabsf(g));
         w -= o.lr_t * m / (v + o.eps);
     }
+    // RowWiseAdagrad's per-row floats (br, bc, the global bias): Keras Adagrad as adagrad_elem, the rounding sequence spelled out so
+    // that the single-GPU apply and the packed apply give the same bits
+    __device__ static void adagrad(float &w, float &a, float g, const OptConsts &o)
+    {
+#pragma clang fp contract(off)
+        a += g * g;
+        w -= o.lr * g * inv_sqrt_eps(a, o.eps);
+    }
     // RMSprop as dense_rmsprop_kernel spells it (a = rms): the entry's rms takes (1 - rho) g^2, the weight moves where g != 0
     __device__ static void rmsprop(float &w, float &a, float g, const OptConsts &o)
     {
@@ -1444,10 +1474,13 @@ struct OptElem {
     }
     // (nk: Nadam's constants of this step — the touched-rows exchange only: apply_packed_kernel; a = m, b = v.  Adam: a = m,
     // b = v, o.lr_t of this step — the touched-rows exchange only, the rows no list names take the sweep's G = 0 update.
-    // LazyAdam: Adam's element update on the touched rows alone, no sweep anywhere: every other row keeps its bits)
+    // LazyAdam: Adam's element update on the touched rows alone, no sweep anywhere: every other row keeps its bits.
+    // RowWiseAdagrad: the variables that are one float per row anyway — br, bc, the global bias — take plain Adagrad; the
+    // embedding rows never come here: rowwise_adagrad_row)
     __device__ static void one(float &w, float &a, float &b, float g, const OptConsts &o, const NadamConsts &nk)
     {
-        if (OPT == GLOVE_OPT_SGD) sgd(w, a, g, o);
+        if (OPT == GLOVE_OPT_ROWWISE_ADAGRAD) adagrad(w, a, g, o);
+        else if (OPT == GLOVE_OPT_SGD) sgd(w, a, g, o);
         else if (OPT == GLOVE_OPT_ADAMAX) adamax(w, a, b, g, o);
         else if (OPT == GLOVE_OPT_ADADELTA) adadelta(w, a, b, g, o);
         else if (OPT == GLOVE_OPT_NADAM) nadam_elem(w, a, b, g, nk);
@@ -1463,7 +1496,7 @@ struct OptElem {
 // Instead the group's LPR lanes look LPR entries up at once — lane t the id, side, bias gradient and mark of the t-th
 // of them — and the rows are then moved two entries at a time, what each needs handed round by lane shuffles: one
 // round trip per pair of entries.
-// OPT: GLOVE_OPT_ADAGRAD, or one of the per-row optimizers (OptElem: SGD, Adamax, Adadelta, Ftrl, LazyAdam) — only touched rows move
+// OPT: GLOVE_OPT_ADAGRAD, or one of the per-row optimizers (OptElem: SGD, Adamax, Adadelta, Ftrl, LazyAdam, RowWiseAdagrad) — only touched rows move
 // under all of them, so the exchange is the same and the epilogue differs.  The dense-decay ones (Nadam, Adam, RMSprop) move
 // every row's slots every step: decay_unmarked_kernel gives the rows no list names their G = 0 update first, and the listed
 // rows take the epilogue here.  s2: the second slot of every variable where the optimizer has one (scalars[2] for the global bias).
@@ -1583,6 +1616,7 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
     constexpr int GPB = kBlock / LPR;
     constexpr bool kAdagrad = OPT == GLOVE_OPT_ADAGRAD;
     constexpr bool kTwo = !kAdagrad && OptSlots<OPT>::two;
+    constexpr bool kRowWise = OptSlots<OPT>::row_wise;          // slot 1 of R / C: one float per row, no slot row to move
     const bool slots = kAdagrad || !(OPT == GLOVE_OPT_SGD && o.momentum == 0.f);     // (plain SGD keeps no slot)
     // t = global_step as the passes of this step left it (Adamax: lr_t = lr / (1 - beta1^t), as apply_sparse_opt_kernel)
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
@@ -1618,15 +1652,15 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
             int todo[2];
             int32_t id[2];
             bool is_row[2];
-            float Gb[2], bval[2], Ab[2], Bb[2];
-            f4 G[2][NV], Wv[2][NV], A[2][NV], Bv[2][kTwo ? NV : 1];
+            float Gb[2], bval[2], Ab[2], Bb[2], Ar[2];
+            f4 G[2][NV], Wv[2][NV], A[2][kRowWise ? 1 : NV], Bv[2][kTwo ? NV : 1];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 todo[e] = __shfl(todo_l, tt + e, LPR);
                 id[e] = __shfl(id_l, tt + e, LPR);
                 is_row[e] = __shfl(row_l, tt + e, LPR) != 0;
                 Gb[e] = __shfl(gb_l, tt + e, LPR);
-                Ab[e] = Bb[e] = 0.f;
+                Ab[e] = Bb[e] = Ar[e] = 0.f;
             }
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
@@ -1647,7 +1681,8 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
                 load_row<LPR, NV>(Wv[e], W, id[e], d4, lg);
                 bval[e] = (is_row[e] ? rs.bias : cs.bias)[id[e]];
                 if (slots) {
-                    load_row<LPR, NV>(A[e], S1, id[e], d4, lg);
+                    if constexpr (kRowWise) Ar[e] = S1[id[e]];                      // one float per id, every lane of the group
+                    else load_row<LPR, NV>(A[e], S1, id[e], d4, lg);
                     Ab[e] = (is_row[e] ? rs.S1b : cs.S1b)[id[e]];
                 }
                 if constexpr (kTwo) {
@@ -1662,6 +1697,9 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
                 if constexpr (kAdagrad) {
 #pragma unroll
                     for (int kk = 0; kk < NV; ++kk) adagrad_vec(Wv[e][kk], A[e][kk], G[e][kk], k.lr, k.eps);
+                } else if constexpr (kRowWise) {
+                    // (the whole group holds entry e and then entry e + 1, one after the other: the group's sum is this entry's alone)
+                    rowwise_adagrad_row<LPR, NV>(Wv[e], Ar[e], G[e], k.lr, k.eps, k.inv_d);
                 } else {
 #pragma unroll
                     for (int kk = 0; kk < NV; ++kk) {
@@ -1677,10 +1715,13 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
                         if constexpr (kTwo) Bv[e][kk] = f4{bb[0], bb[1], bb[2], bb[3]};
                     }
                 }
-                if (slots) store_row<LPR, NV>(S1, (size_t)id[e], d4, lg, A[e]);
+                if constexpr (!kRowWise) {
+                    if (slots) store_row<LPR, NV>(S1, (size_t)id[e], d4, lg, A[e]);
+                }
                 if constexpr (kTwo) store_row<LPR, NV>(is_row[e] ? s2.R : s2.C, (size_t)id[e], d4, lg, Bv[e]);
                 store_row<LPR, NV>(W, (size_t)id[e], d4, lg, Wv[e]);
                 if (lg == 0) {
+                    if constexpr (kRowWise) S1[id[e]] = Ar[e];
                     if constexpr (kAdagrad) adagrad_elem(bval[e], Ab[e], Gb[e], k.lr, k.eps);
                     else OptElem<OPT>::one(bval[e], Ab[e], Bb[e], Gb[e], o, nk);
                     if (slots) (is_row[e] ? rs.S1b : cs.S1b)[id[e]] = Ab[e];
@@ -2504,7 +2545,9 @@ __global__ __launch_bounds__(kBlock) void dense_adam_kernel(
 // The other Keras optimizers `tf.keras.optimizers.get(name)` resolves (reference src/models/train_utils.py:13-16), as apply
 // epilogues on the same traversal as AdagradApply.  Semantics: include/glove_hip.h glove_hyper.optimizer; restated in
 // oracle/glove_ref.py (_sgd, _rmsprop_dense_decay, _adamax).  LazyAdam (GLOVE_OPT_LAZYADAM, this build's addition: Adam's update
-// on the touched rows alone) is the one epilogue here that is no Keras-legacy name; restated in tests/lazyadam_ref.py.
+// on the touched rows alone) and RowWiseAdagrad (GLOVE_OPT_ROWWISE_ADAGRAD: one accumulator per embedding row, fed by the row's
+// mean squared gradient) are the epilogues here that are no Keras-legacy names; restated in tests/lazyadam_ref.py and
+// tests/rowwise_adagrad_ref.py.
 // ------------------------------------------------------------------------------------------
 template <int LPR, int NV, int OPT>
 struct SparseOptApply {
@@ -2512,11 +2555,17 @@ struct SparseOptApply {
     SlotTwo s2;
     int d4, lg;
     OptConsts o;
-    struct State { f4 A[NV], B[NV]; float Ab, Bb; };
+    float inv_d;                        // 1 / d_model (RowWiseAdagrad's mean over the row's real columns)
+    struct State { f4 A[NV], B[NV]; float Ab, Bb, Ar; };        // Ar: RowWiseAdagrad's one accumulator of the row
     __device__ void prefetch(bool is_row, int32_t id, State &st) const
     {
         const SideBufs &sb = is_row ? rs : cs;
         if (OPT == GLOVE_OPT_SGD && o.momentum == 0.f) return;
+        if constexpr (OptSlots<OPT>::row_wise) {
+            st.Ar = sb.S1[id];          // one float per id: no slot row is read
+            st.Ab = sb.S1b[id];
+            return;
+        }
         load_row<LPR, NV>(st.A, sb.S1, id, d4, lg);
         st.Ab = sb.S1b[id];
         if (OptSlots<OPT>::two) {
@@ -2528,6 +2577,19 @@ struct SparseOptApply {
     {
         const SideBufs &sb = is_row ? rs : cs;
         const bool slots = !(OPT == GLOVE_OPT_SGD && o.momentum == 0.f);
+        if constexpr (OptSlots<OPT>::row_wise) {
+            // G is the id's finished sum here on both paths of for_each_id (a heavy id: group 0 has added the groups' partial
+            // sums and the activity-L2 term before it calls): the square is of the sum, never a sum of partial squares
+            rowwise_adagrad_row<LPR, NV>(Wv, st.Ar, G, o.lr, o.eps, inv_d);
+            store_row<LPR, NV>(sb.W, (size_t)wid, d4, lg, Wv);
+            if (lg == 0) {
+                OptElem<OPT>::one(bval, st.Ab, st.Bb, Gb, o);
+                sb.S1[id] = st.Ar;
+                sb.S1b[id] = st.Ab;
+                sb.bias[wid] = bval;
+            }
+            return;
+        }
 #pragma unroll
         for (int kk = 0; kk < NV; ++kk) {
             float w[4] = {Wv[kk].x, Wv[kk].y, Wv[kk].z, Wv[kk].w}, a[4] = {st.A[kk].x, st.A[kk].y, st.A[kk].z, st.A[kk].w};
@@ -2562,7 +2624,7 @@ __global__ __launch_bounds__(kBlock) void apply_sparse_opt_kernel(
     if (OPT == GLOVE_OPT_ADAMAX) o.lr_t = o.lr / -expm1f((float)((double)(*step) * ln_beta1));
     if (OPT == GLOVE_OPT_LAZYADAM) o.lr_t = adam_lr_t(o.lr, ln_beta1, ln_beta2, *step);
     const bool scalar_duty = for_each_id<LPR, NV>(wk, rs, cs, d4, k,
-                                                  SparseOptApply<LPR, NV, OPT>{rs, cs, s2, d4, (int)(threadIdx.x % LPR), o});
+                                                  SparseOptApply<LPR, NV, OPT>{rs, cs, s2, d4, (int)(threadIdx.x % LPR), o, k.inv_d});
     if (scalar_duty) {
         float tot[kPartials];
         sum_blockpart(blockpart, nblocks_rowpass, tot);
@@ -2804,7 +2866,9 @@ static int check_optimizer(const glove_tables *t, const glove_hyper *h, int side
 {
     const bool betas = opt == GLOVE_OPT_ADAMAX || opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_LAZYADAM;
     const bool two_slots = betas || opt == GLOVE_OPT_ADADELTA || opt == GLOVE_OPT_FTRL;
-    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && !two_slots) return GLOVE_E_BADARG;
+    // (RowWiseAdagrad: one slot — s1_R / s1_C are float[rows] —, no hyper-parameter of its own beside Adagrad's epsilon)
+    if (opt != GLOVE_OPT_ADAGRAD && opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_RMSPROP && opt != GLOVE_OPT_ROWWISE_ADAGRAD && !two_slots)
+        return GLOVE_E_BADARG;
     if ((sides & 1) && (!t->s1_R || !t->s1_br || (two_slots && (!t->s2_R || !t->s2_br)))) return GLOVE_E_BADARG;
     if ((sides & 2) && (!t->s1_C || !t->s1_bc || (two_slots && (!t->s2_C || !t->s2_bc)))) return GLOVE_E_BADARG;
     if (betas && (!(h->beta1 > 0.0 && h->beta1 < 1.0) || !(h->beta2 > 0.0 && h->beta2 < 1.0) || !t->step)) return GLOVE_E_BADARG;
@@ -3218,6 +3282,7 @@ static int dense_common(const glove_tables *t, const glove_hyper *h, float *G_fl
 int glove_dense_adagrad_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
 {
     DenseSegs segs; float *tail; int nbx, sides;
+    if (h && h->optimizer == GLOVE_OPT_ROWWISE_ADAGRAD) return GLOVE_E_BADARG;      // its table slots are float[rows]: nothing to sweep
     if (int rc = plain_table(t, stream)) return rc;
     if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
     const StepConsts k = make_consts(t, h);
@@ -3230,7 +3295,8 @@ int glove_dense_adagrad_f32(const glove_tables *t, const glove_hyper *h, float *
 int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
 {
     DenseSegs segs; float *tail; int nbx, sides;
-    if (h && h->optimizer == GLOVE_OPT_LAZYADAM) return GLOVE_E_BADARG;      // touched rows only: it has no dense sweep
+    // touched rows only: no dense sweep (RowWiseAdagrad's table slots are not even shaped like the tables a sweep walks)
+    if (h && (h->optimizer == GLOVE_OPT_LAZYADAM || h->optimizer == GLOVE_OPT_ROWWISE_ADAGRAD)) return GLOVE_E_BADARG;
     if (int rc = plain_table(t, stream)) return rc;
     if (h && h->optimizer == GLOVE_OPT_RMSPROP) {
         // the other dense-decay optimizer of the Keras set: its whole rms slot decays every step, entries with a gradient move —
@@ -3474,7 +3540,7 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         const int scal = first == 0 ? do_scalars : 0;
 #define CALL(LPR, NV)                                                                                                         \
         dispatch_opt<GLOVE_OPT_ADAGRAD, GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_NADAM, GLOVE_OPT_ADAM,  \
-                     GLOVE_OPT_RMSPROP, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM>(opt, [&](auto o_) {                               \
+                     GLOVE_OPT_RMSPROP, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM, GLOVE_OPT_ROWWISE_ADAGRAD>(opt, [&](auto o_) {    \
             hipLaunchKernelGGL((apply_packed_kernel<LPR, NV, decltype(o_)::value>), dim3(nbx, pls.n), dim3(kBlock), 0, st, pls, dv, rs, \
                                cs, s2, d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars,    \
                                loss_out, scal);                                                                               \
@@ -3796,13 +3862,14 @@ int glove_step_adam_f32(const glove_plan *p, const glove_tables *t, const glove_
     return glove_dense_adam_f32(t, h, G_flat, loss_out, stream);
 }
 
-// A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam): the passes of `sides`, then apply_sparse_opt_kernel on their ids
+// A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam, RowWiseAdagrad): the passes of `sides`, then apply_sparse_opt_kernel on their ids
 // (1: the row ids alone, no scalar work)
 static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                                   int sides, float *loss_out, void *stream)
 {
     const int opt = h->optimizer;
-    if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL && opt != GLOVE_OPT_LAZYADAM)
+    if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL && opt != GLOVE_OPT_LAZYADAM &&
+        opt != GLOVE_OPT_ROWWISE_ADAGRAD)
         return GLOVE_E_BADARG;
     if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, sides)) return rc;
     const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
@@ -3817,7 +3884,8 @@ static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, co
     const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
     const OptHyper oh = opt_consts(h);
 #define CALL(LPR, NV)                                                                                                      \
-    dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM>(opt, [&](auto o_) { \
+    dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM,                  \
+                 GLOVE_OPT_ROWWISE_ADAGRAD>(opt, [&](auto o_) {                                                           \
         hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, \
                            slot_two(t), d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,            \
                            (const float *)w.blockpart, nb_row, loss_out);                                                 \

@@ -21,7 +21,8 @@ LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
 GLOVE_ABI_VERSION = 15
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7,
-                   "LazyAdam": 8}      # glove_hyper.optimizer (GLOVE_OPT_*); LazyAdam is this build's addition, no Keras-legacy name
+                   "LazyAdam": 8, "RowWiseAdagrad": 9}      # glove_hyper.optimizer (GLOVE_OPT_*); LazyAdam and RowWiseAdagrad are this build's additions, no Keras-legacy names
+ROW_WISE_OPTIMIZERS = ("RowWiseAdagrad",)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
 STEP_AUTO, STEP_TWO_LAUNCH, STEP_FUSED_ONE_PASS, STEP_FUSED_THREE_LAUNCH, STEP_FUSED_TWIN, STEP_TAGGED = 0, 1, 2, 3, 4, 5   # glove_hyper.step_form (2: tests / comparisons only)
 TAGGED_STEP_MAX_BATCH = 2048      # GLOVE_STEP_AUTO takes the tagged step up to this batch size on step-tagged tables
 DEFAULT_CHUNK_CAP = 32
@@ -279,13 +280,15 @@ class DeviceTables:
         self.s1, self.s2 = {}, {}
         for n in self.NAMES:
             w = getattr(self, n)
-            if optimizer in ("Adagrad", "Ftrl"):
+            if optimizer in ROW_WISE_OPTIMIZERS:       # one accumulator per row: float[rows] for R and C as for br and bc
+                self.s1[n] = torch.full((w.shape[0],), 0.1, dtype=torch.float32, device=self.device)
+            elif optimizer in ("Adagrad", "Ftrl"):
                 self.s1[n] = torch.full_like(w, 0.1)   # initial_accumulator_value (both optimizers' Keras default)
             else:                                      # Adam / LazyAdam m / v, Adamax m / v, Adadelta accum_grad / accum_var; SGD momentum accumulator, RMSprop rms: zeros
                 self.s1[n] = torch.zeros_like(w)
             if optimizer in ("Adam", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam"):
                 self.s2[n] = torch.zeros_like(w)       # (Ftrl: linear)
-        if optimizer in ("Adagrad", "Ftrl"):
+        if optimizer in ("Adagrad", "Ftrl") + ROW_WISE_OPTIMIZERS:
             self.scalars[1] = 0.1
         if optimizer == "Nadam":
             self.scalars[4:6] = 1.0                    # the momentum cache (Keras: an optimizer weight initialised to ones)
@@ -422,6 +425,7 @@ class DeviceTables:
         return getattr(self, name)[:, :self.d_model]
 
     # ---- (de)serialisation used by the checkpoint code and the tests: logical shapes [rows, d_model]
+    # (a slot need not be shaped like its variable: RowWiseAdagrad's slot 1 of R and C is float[rows] — 1-D arrays pass whole)
     def _logical(self, x):
         return (x[:, :self.d_model] if x.dim() == 2 else x).cpu()
 
@@ -1116,7 +1120,7 @@ class GloveHip:
                "glove_step_adam_f32")
 
     def step_sparse(self, plan, tables, hyper, G_flat=None, loss_out=None, ws=None):
-        """One step under the Keras optimizer `tables.optimizer` names (glove_step_sparse_f32: SGD, RMSprop, Adamax, Adadelta, Ftrl, Nadam, LazyAdam; Adagrad
+        """One step under the Keras optimizer `tables.optimizer` names (glove_step_sparse_f32: SGD, RMSprop, Adamax, Adadelta, Ftrl, Nadam, LazyAdam, RowWiseAdagrad; Adagrad
         and Adam go to their own entry points).  G_flat: the dense gradient buffer RMSprop, Nadam and Adam need."""
         ws = self.step_workspace(plan, tables.d) if ws is None else ws
         hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]

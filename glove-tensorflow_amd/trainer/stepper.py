@@ -353,9 +353,10 @@ class Stepper(GraphedSteps):
     exchange, whose apply takes their epilogue; the dense-decay ones (Adam, RMSprop: every row's slots move every step) on
     the dense all-reduce.  Nadam (m, v decay everywhere, touched rows move) rides the touched-rows exchange too: the lists
     ARE the union of the ranks' ids — the rows no list names decay (a sweep in front of the apply), the named ones move.
-    LazyAdam (this build's addition, not a Keras name: Adam on the touched rows alone) is one of the per-row ones."""
+    LazyAdam (this build's addition, not a Keras name: Adam on the touched rows alone) is one of the per-row ones, and so is
+    RowWiseAdagrad (one Adagrad accumulator per embedding row: its table slots are float[rows], nothing a dense sweep could walk)."""
 
-    ROWS_ONLY = ("SGD", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam")       # touched-rows exchange (the lists carry the union of the ids)
+    ROWS_ONLY = ("SGD", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam", "RowWiseAdagrad")       # touched-rows exchange (the lists carry the union of the ids)
     DENSE_ONLY = ("Adam", "RMSprop")                        # dense-decay optimizers: dense all-reduce
 
     def __init__(self, backend, tables, hyper_kwargs: dict, batch_size: int, world=1, dist=None, exchange="auto",
@@ -375,7 +376,7 @@ class Stepper(GraphedSteps):
         if exchange == "dense" and self._multi and tables.optimizer in self.ROWS_ONLY:
             raise ValueError("%s runs on the touched-rows exchange (its dense form would need the ranks' id marks)" % tables.optimizer)
         if self._multi and tables.optimizer not in ("Adagrad",) + self.ROWS_ONLY + self.DENSE_ONLY:
-            raise ValueError("the data-parallel form takes the eight Keras names (Adagrad, SGD, Adamax, Adadelta, Ftrl, Nadam, Adam, RMSprop) and LazyAdam, got %s" % tables.optimizer)
+            raise ValueError("the data-parallel form takes the eight Keras names (Adagrad, SGD, Adamax, Adadelta, Ftrl, Nadam, Adam, RMSprop), LazyAdam and RowWiseAdagrad, got %s" % tables.optimizer)
         if self._multi and tables.optimizer in self.ROWS_ONLY:
             exchange = "rows"
         self.hyper = backend.make_hyper(batch_size=batch_size * self.world, **hyper_kwargs)
@@ -489,7 +490,7 @@ def route_by_row_owner(coo: dict, world: int, rank: int, dist) -> dict:
 
 
 KERAS_OPTIMIZERS = ("Adagrad", "SGD", "RMSprop", "Adamax", "Adam", "Adadelta", "Ftrl", "Nadam")
-SHARDED_OPTIMIZERS = KERAS_OPTIMIZERS + ("LazyAdam",)       # what the sharded forms take: LazyAdam rides the lists like Adamax
+SHARDED_OPTIMIZERS = KERAS_OPTIMIZERS + ("LazyAdam", "RowWiseAdagrad")       # what the sharded forms take: both additions ride the lists like Adamax
 
 
 def plain_step_phases(backend, tables, hyper, loss_out, G):
@@ -512,7 +513,7 @@ def sharded_exchange(tables, exchange: str, multi: bool) -> str:
     """The col-side exchange a row-sharded form takes for `tables.optimizer`: the per-row optimizers and Nadam (only
     touched rows move) need the lists — the union of the ranks' ids —, Adagrad, Adam and RMSprop take either."""
     if tables.optimizer not in SHARDED_OPTIMIZERS:
-        raise ValueError("the sharded forms take the eight Keras names (%s) and LazyAdam, got %s" % (", ".join(KERAS_OPTIMIZERS), tables.optimizer))
+        raise ValueError("the sharded forms take the eight Keras names (%s), LazyAdam and RowWiseAdagrad, got %s" % (", ".join(KERAS_OPTIMIZERS), tables.optimizer))
     if exchange not in ("auto", "dense", "rows"):
         raise ValueError("exchange must be auto, dense or rows")
     if multi and tables.optimizer in Stepper.ROWS_ONLY:

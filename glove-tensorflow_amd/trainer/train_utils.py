@@ -24,6 +24,8 @@ OPTIMIZERS = {
     "Adam": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},
     # not a Keras-legacy name: Adam that moves only the rows a batch touches (include/glove_hip.h GLOVE_OPT_LAZYADAM)
     "LazyAdam": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},
+    # not a Keras-legacy name either: Adagrad with ONE accumulator per embedding row (include/glove_hip.h GLOVE_OPT_ROWWISE_ADAGRAD)
+    "RowWiseAdagrad": {"initial_accumulator_value": 0.1, "epsilon": 1e-7},
     "SGD": {"momentum": 0.0, "nesterov": False},
     "RMSprop": {"rho": 0.9, "momentum": 0.0, "epsilon": 1e-7, "centered": False},
     "Adamax": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},

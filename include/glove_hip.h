@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GLOVE_ABI_VERSION 15   /* 15: GLOVE_OPT_LAZYADAM (Adam on the touched rows alone, this build's addition) in glove_step_sparse_f32, glove_rowside_step_f32 and glove_apply_packed_adagrad_f32; no entry point added; 14: glove_hyper.sweep_sides; glove_apply_packed_adagrad_f32 takes GLOVE_OPT_ADAM and GLOVE_OPT_RMSPROP and applies the dense-decay optimizers (Adam, RMSprop, Nadam) to one side; glove_dense_adam_f32 applies RMSprop to one side; glove_rowside_step_f32 (the row side of a step under any of the eight optimizers): the sharded multi-GPU forms run every Keras optimizer; 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
+#define GLOVE_ABI_VERSION 15   /* 15: GLOVE_OPT_LAZYADAM (Adam on the touched rows alone, this build's addition) in glove_step_sparse_f32, glove_rowside_step_f32 and glove_apply_packed_adagrad_f32; no entry point added — 15 now also covers GLOVE_OPT_ROWWISE_ADAGRAD (one Adagrad accumulator per embedding row: glove_tables.s1_R / s1_C are float[rows] under it), an additive enum value taken by the same three entry points: no struct field, no export, no changed meaning of an existing value; 14: glove_hyper.sweep_sides; glove_apply_packed_adagrad_f32 takes GLOVE_OPT_ADAM and GLOVE_OPT_RMSPROP and applies the dense-decay optimizers (Adam, RMSprop, Nadam) to one side; glove_dense_adam_f32 applies RMSprop to one side; glove_rowside_step_f32 (the row side of a step under any of the eight optimizers): the sharded multi-GPU forms run every Keras optimizer; 13: pruned — glove_plan_build_many, glove_shuffle_stream, glove_steps_rebuilt_f32 (+ glove_build_ring) are gone; glove_dense_grad_floats, glove_packed_entry_floats and glove_fused_step_bytes are what glove_dense_grad_layout returns and the macros GLOVE_PACKED_ENTRY_FLOATS / GLOVE_FUSED_STEP_BYTES; 12: glove_plan.r_chunk_hw / c_chunk_hw (the fused step forms on plans without records); 11: glove_plan.r_mark / c_mark (bitmaps of the batch's ids), the tagged form of glove_step(s)_adam_f32; 10: glove_hyper.optimizer / momentum / nesterov / rho, glove_step_sparse_f32 (SGD, RMSprop, Adamax, later Adadelta and Ftrl by their Keras names); 9: tagged step on step-tagged twinned tables (glove_tables.R_tag / C_tag, GLOVE_STEP_TAGGED); 8: epochs dealt from id-sorted master orders (glove_masters_build, glove_epoch_deal, glove_plan_build_sorted); plans whose pair fields live in their chunk records only; 7: chunk records start on 128-byte lines (capacity per record changed), glove_plan_build_many, glove_shuffle_stream; 6: glove_steps_rebuilt_f32; 5: record layout in 8-pair blocks; packing passes, loss partials */
 
 #define GLOVE_E_BADARG   (-1)   /* null pointer / non-positive size / d % 4 != 0 */
 #define GLOVE_E_WORKSPACE (-2)  /* workspace or plan storage too small */
@@ -45,7 +45,7 @@ typedef struct glove_tables {
                                  * keeps them exactly zero, so dots, norms and gradients ignore them */
     float *R, *C;               /* row_embedding / col_embedding [V,d] (model_utils.py:31-34) */
     float *br, *bc;             /* row_bias / col_bias [V]         (model_utils.py:32-36) */
-    float *s1_R, *s1_C, *s1_br, *s1_bc;   /* slot 1, same shapes */
+    float *s1_R, *s1_C, *s1_br, *s1_bc;   /* slot 1, same shapes (GLOVE_OPT_ROWWISE_ADAGRAD: s1_R float[V_row], s1_C float[V]) */
     float *s2_R, *s2_C, *s2_br, *s2_bc;   /* slot 2 (Adam only; may be NULL for Adagrad) */
     /* scalars live on the device so that a captured hipGraph replays without host patching:
      *  [0] global_bias g (model_utils.py:39)  [1] slot1(g)  [2] slot2(g)  [3] which copy of twinned tables is current as a
@@ -157,7 +157,18 @@ typedef struct glove_hyper {
      *                      t = global_step as this step's row pass advanced it — the GLOBAL step even for a row last touched
      *                      long ago, not a per-row counter.  Rows the batch does not touch keep var, m and v bit for bit.
      *                      The global bias is a dense variable: it takes the plain Adam update every step (scalars[1],
-     *                      scalars[2]).  No sweep, no marks, no G_flat; never the one-launch or tagged forms */
+     *                      scalars[2]).  No sweep, no marks, no G_flat; never the one-launch or tagged forms
+     *   GLOVE_OPT_ROWWISE_ADAGRAD (slot1 = accumulator, 0.1; epsilon 1e-7) NOT a Keras-legacy name: row-wise Adagrad as FBGEMM /
+     *                      TorchRec apply it to embedding tables — ONE accumulator per embedding row.  glove_tables.s1_R is
+     *                      float[V_row] and s1_C float[V] (indexed by id, not by id * d); s1_br / s1_bc are as under Adagrad; there
+     *                      is no slot 2.  For each distinct id u of the batch, on each side, with G[u, :] its summed gradient
+     *                      (activity-L2 term included) over the d_model real columns:
+     *                      A[u] += (sum_j G[u, j]^2) / d_model;  W[u, :] -= lr G[u, :] / (sqrt(A[u]) + epsilon), A[u] as
+     *                      incremented.  The padding columns d_model .. d-1 hold G = 0 and stay exactly zero.  br and bc are one
+     *                      float per row already: plain Adagrad on the touched ids; the global bias takes the dense Adagrad
+     *                      update every step (scalars[1]).  Rows the batch does not touch keep W and A bit for bit.  The row sum
+     *                      has a fixed order: a step is bitwise repeatable.  No sweep, no marks, no G_flat; never the fused,
+     *                      twin, tagged or one-launch forms; glove_dense_adagrad_f32 and glove_dense_adam_f32 refuse it */
     int32_t optimizer;
     float momentum;             /* SGD, Keras default 0 */
     int32_t nesterov;           /* SGD, Keras default 0 */
@@ -179,6 +190,7 @@ typedef struct glove_hyper {
 #define GLOVE_OPT_FTRL 6
 #define GLOVE_OPT_NADAM 7
 #define GLOVE_OPT_LAZYADAM 8
+#define GLOVE_OPT_ROWWISE_ADAGRAD 9
 
 #define GLOVE_HEAD_REGRESSION 0
 #define GLOVE_HEAD_LOGISTIC 1
@@ -428,7 +440,7 @@ int glove_count_packed_f32(const glove_packed_list *lists, int32_t n_lists, cons
 int glove_combine_packed_f32(const glove_packed_list *list, int32_t tag, const glove_tables *t, float *G_flat,
                              int32_t *mark, int64_t capacity_entries, void *stream);
 /* The optimizer glove_hyper.optimizer names — Adagrad, or one of the per-row optimizers (GLOVE_OPT_SGD, _ADAMAX, _ADADELTA,
- * _FTRL, _LAZYADAM: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*), or one
+ * _FTRL, _LAZYADAM, _ROWWISE_ADAGRAD: only touched rows move under them, so they ride the same exchange; their second slots are glove_tables.s2_*), or one
  * of the dense-decay ones, whose slots move on every row every step: first the rows NO list names on the sides
  * glove_hyper.sweep_sides selects take their G = 0 update (GLOVE_OPT_NADAM: m and v decay; GLOVE_OPT_ADAM: m and v decay and
  * the row moves, lr_t of t = global_step; GLOVE_OPT_RMSPROP: the rms slot decays) — which needs the lists counted into `mark`
@@ -460,7 +472,7 @@ int glove_rowside_step_adagrad_f32(const glove_plan *plan, const glove_tables *t
  * bias, loss and Nadam's momentum cache go with the col side's apply).  Adagrad: glove_rowside_step_adagrad_f32.  Adam, Nadam:
  * the row pass marks the batch's row ids in G_flat, then one kernel applies the row ids and gives every other row of the row
  * table its G = 0 update (m and v decay; Adam: the row moves too), clearing the marks.  RMSprop: the row pass, the summed row
- * gradients into G_flat, the sweep over the row table's rms slot.  SGD, Adamax, Adadelta, Ftrl, LazyAdam: the row pass, then their
+ * gradients into G_flat, the sweep over the row table's rms slot.  SGD, Adamax, Adadelta, Ftrl, LazyAdam, RowWiseAdagrad: the row pass, then their
  * epilogue on the row ids.  t = global_step as this call's row pass advanced it.  G_flat, all zero on entry and on return:
  * Adam, Nadam: V_row floats (the marks); RMSprop: the row half [G_R | G_br] of the glove_dense_grad_layout layout for these
  * tables (the start of a whole dense gradient buffer serves both); unused by Adagrad and the per-row ones.
