@@ -421,6 +421,49 @@ class Estimator:
         logger.info("eval at global_step %d: average_loss = %.6f", rec["global_step"], rec["average_loss"])
         return rec
 
+    # ---- word analogies (this build only: the reference has no intrinsic measure of the embeddings)
+    def evaluate_analogies(self, questions, embeddings="row", top_k=1, batch_size=1024, restrict_vocab=None,
+                           lowercase=True) -> dict:
+        """Scores the analogy questions `a : b :: c : ?` of the file `questions` (trainer.analogy: the format and the
+        counts) by 3CosAdd on the GPU (include/glove_eval_hip.h) and writes job_dir/eval/analogy.json.  `embeddings`:
+        the row table, the col table or their sum, the GloVe paper's W + W~; `restrict_vocab` N: the first N rows are
+        the table and the candidates.  One process, on the whole model."""
+        from trainer import analogy
+        from trainer.data_utils import read_vocab
+        if self.world > 1:
+            raise ValueError("evaluate_analogies runs in one process: checkpoints hold the whole model")
+        if embeddings not in analogy.EMBEDDINGS:
+            raise ValueError("--embeddings must be one of %s, got %r" % (", ".join(analogy.EMBEDDINGS), embeddings))
+        tables = self.model.tables
+        W = {"row": lambda: tables.R, "col": lambda: tables.C, "sum": lambda: tables.R + tables.C}[embeddings]()
+        if restrict_vocab is not None:
+            if not 0 < restrict_vocab <= self.vocab_size:
+                raise ValueError("--restrict-vocab must lie in [1, %d], got %r" % (self.vocab_size, restrict_vocab))
+            W = W[:restrict_vocab]
+        W = W.contiguous()
+        if not 1 <= top_k <= min(W.shape[0] - 3, 1024):
+            raise ValueError("--top-k must lie in [1, min(rows - 3, 1024)] (a question's own three words are no candidates): "
+                             "%d rows, got %r" % (W.shape[0], top_k))
+        sections = analogy.parse_questions(questions, lowercase=lowercase)
+        kept, counts = analogy.lookup_questions(sections, read_vocab(self.params["vocab_txt"]), limit=restrict_vocab)
+        if kept:
+            abc = torch.tensor([q[:3] for q in kept], dtype=torch.int32).to(self.device)
+            _, idx = self.backend.analogy_topk(W, abc, top_k, batch_size)
+            expected = torch.tensor([q[3] for q in kept], dtype=torch.int32)
+            hits = (idx.cpu() == expected[:, None]).any(dim=1).tolist()
+        else:
+            hits = []
+        rec = {"global_step": tables.global_step, "embeddings": embeddings, "top_k": top_k}
+        rec.update(analogy.summarize(sections, counts, hits))
+        for s in rec["sections"] + [dict(rec["total"], name="total")]:
+            logger.info("analogies, %s: %d of %d correct%s, %d skipped", s["name"] or "(unnamed)", s["correct"], s["total"],
+                        "" if s["accuracy"] is None else " (%.2f %%)" % (100 * s["accuracy"]), s["skipped"])
+        path = os.path.join(self.params["job_dir"], "eval", "analogy.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(rec, f, indent=2)
+        return rec
+
     # ---- PREDICT
     def _vocabulary_order_model(self):
         """What PREDICT addresses by vocabulary id: the model itself, or — a sharded run — the whole row table gathered from

@@ -1,4 +1,4 @@
-"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h).
+"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h) and of libglove_eval_hip.so (include/glove_eval_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -17,8 +17,10 @@ logger = logging.getLogger(__name__)
 
 PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
+EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_eval_hip.h: scoring finished embeddings, a library of its own
 
 GLOVE_ABI_VERSION = 15
+GLOVE_EVAL_ABI_VERSION = 1
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7,
                    "LazyAdam": 8, "RowWiseAdagrad": 9}      # glove_hyper.optimizer (GLOVE_OPT_*); LazyAdam and RowWiseAdagrad are this build's additions, no Keras-legacy names
@@ -59,6 +61,9 @@ EXPORTED_SYMBOLS = (
     "glove_plan_sorted_workspace_bytes", "glove_plan_chunk_bound", "glove_plan_build_sorted", "glove_step_sparse_f32",
     "glove_rowside_step_f32",
 )
+
+# every symbol include/glove_eval_hip.h declares
+EVAL_EXPORTED_SYMBOLS = ("glove_eval_abi_version", "glove_analogy_workspace_bytes", "glove_analogy_topk_f32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -176,6 +181,37 @@ def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CD
         raise GloveHipError("ABI mismatch: library %d, binding %d" % (lib.glove_abi_version(), GLOVE_ABI_VERSION))
     if path is None:
         _lib = lib
+    return lib
+
+
+_eval_lib = None
+
+
+def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
+    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h) and declare the prototypes, at the first call that needs it:
+    training never loads it.  Raises if it is not built, like load_library."""
+    global _eval_lib
+    if _eval_lib is not None and path is None:
+        return _eval_lib
+    p = Path(path) if path else EVAL_LIB_PATH
+    if not p.exists():
+        raise GloveHipError(
+            "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). There is no CPU fallback." % p)
+    lib = C.CDLL(str(p))
+    sz, i32, vp = C.c_size_t, C.c_int32, C.c_void_p
+    protos = {
+        "glove_eval_abi_version": (C.c_int, []),
+        "glove_analogy_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "glove_analogy_topk_f32": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+    }
+    for name, (res, args) in protos.items():
+        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        fn.restype, fn.argtypes = res, args
+    if lib.glove_eval_abi_version() != GLOVE_EVAL_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: eval library %d, binding %d" % (lib.glove_eval_abi_version(), GLOVE_EVAL_ABI_VERSION))
+    if path is None:
+        _eval_lib = lib
     return lib
 
 
@@ -1174,6 +1210,28 @@ class GloveHip:
         ws = torch.empty(self.lib.glove_topk_workspace_bytes(n, V, k), dtype=torch.uint8, device=R.device)
         _check(self.lib.glove_topk_cosine_f32(_ptr(R), V, d, _ptr(query_ids), n, k, _ptr(sims), _ptr(idx),
                                               _ptr(ws), ws.numel(), _stream()), "glove_topk_cosine_f32")
+        return sims, idx
+
+    def analogy_topk(self, W: torch.Tensor, abc: torch.Tensor, k: int, batch: int = 1024):
+        """3CosAdd word analogies (include/glove_eval_hip.h): for the questions abc [n,3] = (a, b, c) the k rows of W [V,d]
+        closest by cosine to w^_b - w^_a + w^_c, a, b and c themselves left out -> (sims, idx) [n,k], descending, ties to
+        the lower id.  The scores of `batch` questions are a [batch, V] matrix in the workspace: the questions are walked
+        in batches of that size through one workspace.  The ids of abc must lie in [0, V): the kernels do not look."""
+        _require(W, torch.float32); _require(abc, torch.int32)
+        if W.dim() != 2 or abc.dim() != 2 or abc.shape[1] != 3:
+            raise GloveHipError("expected W [V,d] and abc [n,3]")
+        if batch < 1:
+            raise GloveHipError("batch must be positive, got %d" % batch)
+        lib = load_eval_library()
+        V, d = W.shape
+        n = int(abc.shape[0])
+        sims = torch.empty(n, k, dtype=torch.float32, device=W.device)
+        idx = torch.empty(n, k, dtype=torch.int32, device=W.device)
+        ws = torch.empty(max(lib.glove_analogy_workspace_bytes(min(batch, n), V, d, k), 256), dtype=torch.uint8, device=W.device)
+        for s in range(0, max(n, 1), batch):      # (n == 0: one call, which checks the sizes and launches nothing)
+            m = min(batch, n - s)
+            _check(lib.glove_analogy_topk_f32(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, _ptr(sims[s:s + m]), _ptr(idx[s:s + m]),
+                                              _ptr(ws), ws.numel(), _stream()), "glove_analogy_topk_f32")
         return sims, idx
 
     # ---- data prep

@@ -207,6 +207,9 @@ class HipBackend:
     def topk_cosine(self, R, query_ids, k):
         return self.hip.topk_cosine(R, query_ids, k)
 
+    def analogy_topk(self, W, abc, k, batch=1024):
+        return self.hip.analogy_topk(W, abc, k, batch)
+
 
 def all_gather_rows(dist, recv, send, async_op=False):
     """recv[r] = rank r's `send` (equal shapes).  async_op: returns the work handle (wait() before reading recv)."""
