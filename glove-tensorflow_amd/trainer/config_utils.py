@@ -18,6 +18,7 @@ from pathlib import Path
 from typing import NamedTuple
 
 from trainer import config
+from trainer.optimizers import OPTIMIZERS, names
 
 logger = logging.getLogger(__name__)
 
@@ -46,9 +47,8 @@ FLAGS = (
     Flag("embedding-size", int, config.EMBEDDING_SIZE, "columns of the row and column embedding tables"),
     Flag("l2-reg", float, config.L2_REG, "activity-L2 coefficient"),
     Flag("neg-factor", float, config.NEG_FACTOR, "weight of the negative head's loss (logistic heads)"),
-    Flag("optimizer", str, config.OPTIMIZER, "Keras optimizer name: Adagrad, Adam, SGD, RMSprop, Adamax, Nadam, Adadelta or Ftrl; LazyAdam "
-                             "(this build's addition: Adam on the rows a batch touches only) or RowWiseAdagrad (this build's addition: "
-                             "Adagrad with one accumulator per embedding row)"),
+    Flag("optimizer", str, config.OPTIMIZER, "Keras optimizer name: %s; or this build's additions: %s" % (
+        ", ".join(names(lambda o: o.keras)), ", ".join("%s (%s)" % (o.name, o.about) for o in OPTIMIZERS.values() if not o.keras))),
     Flag("learning-rate", float, config.LEARNING_RATE, "optimizer step size"),
     Flag("batch-size", int, config.BATCH_SIZE, "nonzeros per step and rank"),
     Flag("train-steps", int, config.TRAIN_STEPS, "absolute global_step to stop at"),

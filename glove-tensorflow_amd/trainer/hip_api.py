@@ -13,6 +13,8 @@ from pathlib import Path
 
 import torch
 
+from trainer.optimizers import BY_CODE, OPTIMIZERS, names
+
 logger = logging.getLogger(__name__)
 
 PKG_DIR = Path(__file__).resolve().parent.parent
@@ -22,9 +24,8 @@ EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_ev
 GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
-OPTIMIZER_CODES = {"Adagrad": 0, "SGD": 1, "RMSprop": 2, "Adamax": 3, "Adam": 4, "Adadelta": 5, "Ftrl": 6, "Nadam": 7,
-                   "LazyAdam": 8, "RowWiseAdagrad": 9}      # glove_hyper.optimizer (GLOVE_OPT_*); LazyAdam and RowWiseAdagrad are this build's additions, no Keras-legacy names
-ROW_WISE_OPTIMIZERS = ("RowWiseAdagrad",)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
+OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
+ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
 STEP_AUTO, STEP_TWO_LAUNCH, STEP_FUSED_ONE_PASS, STEP_FUSED_THREE_LAUNCH, STEP_FUSED_TWIN, STEP_TAGGED = 0, 1, 2, 3, 4, 5   # glove_hyper.step_form (2: tests / comparisons only)
 TAGGED_STEP_MAX_BATCH = 2048      # GLOVE_STEP_AUTO takes the tagged step up to this batch size on step-tagged tables
 DEFAULT_CHUNK_CAP = 32
@@ -112,6 +113,21 @@ class GloveHipError(RuntimeError):
 _lib = None
 
 
+def _open(p: Path, protos: dict, optional: bool = False) -> C.CDLL:
+    """dlopen a built library and declare its prototypes (`optional`: symbols an older build lacks are left out)."""
+    if not p.exists():
+        raise GloveHipError(
+            "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(hipcc --offload-arch=gfx950). There is no CPU fallback." % p)
+    lib = C.CDLL(str(p))
+    for name, (res, args) in protos.items():
+        if optional and not hasattr(lib, name):
+            continue
+        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+        fn.restype, fn.argtypes = res, args
+    return lib
+
+
 def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CDLL:
     """dlopen libglove_hip.so and declare the prototypes.  Raises if it is not built.  `path` / `any_abi`: explicit
     arguments of the A/B tools (tools/ab_kernels.py), which load other builds of the library — older ones included —
@@ -119,12 +135,6 @@ def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CD
     global _lib
     if _lib is not None and path is None:
         return _lib
-    p = Path(path) if path else LIB_PATH
-    if not p.exists():
-        raise GloveHipError(
-            "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). There is no CPU fallback." % p)
-    lib = C.CDLL(str(p))
     P = C.POINTER
     sz, i32, i64, vp = C.c_size_t, C.c_int32, C.c_int64, C.c_void_p
     protos = {
@@ -172,11 +182,7 @@ def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CD
         "glove_cooc_workspace_bytes": (sz, [i64, i32]),
         "glove_cooccurrence_i32": (C.c_int, [vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
     }
-    for name, (res, args) in protos.items():
-        if path and any_abi and not hasattr(lib, name):
-            continue
-        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-        fn.restype, fn.argtypes = res, args
+    lib = _open(Path(path) if path else LIB_PATH, protos, optional=bool(path and any_abi))
     if lib.glove_abi_version() != GLOVE_ABI_VERSION and not (path and any_abi):
         raise GloveHipError("ABI mismatch: library %d, binding %d" % (lib.glove_abi_version(), GLOVE_ABI_VERSION))
     if path is None:
@@ -193,21 +199,13 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
     global _eval_lib
     if _eval_lib is not None and path is None:
         return _eval_lib
-    p = Path(path) if path else EVAL_LIB_PATH
-    if not p.exists():
-        raise GloveHipError(
-            "%s not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). There is no CPU fallback." % p)
-    lib = C.CDLL(str(p))
     sz, i32, vp = C.c_size_t, C.c_int32, C.c_void_p
     protos = {
         "glove_eval_abi_version": (C.c_int, []),
         "glove_analogy_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "glove_analogy_topk_f32": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
     }
-    for name, (res, args) in protos.items():
-        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-        fn.restype, fn.argtypes = res, args
+    lib = _open(Path(path) if path else EVAL_LIB_PATH, protos)
     if lib.glove_eval_abi_version() != GLOVE_EVAL_ABI_VERSION:
         raise GloveHipError("ABI mismatch: eval library %d, binding %d" % (lib.glove_eval_abi_version(), GLOVE_EVAL_ABI_VERSION))
     if path is None:
@@ -269,6 +267,19 @@ def row_width(rows: int, d: int) -> int:
     return base
 
 
+def _plain_view(name, rows):
+    """DeviceTables.R / br / C / bc: see there."""
+    def get(self) -> torch.Tensor:
+        self.canonicalize()
+        return getattr(self, "_" + name)[:getattr(self, rows)]
+
+    def put(self, value):               # `tables.R += x` and `tables.R = tensor` write into the buffer the kernels see
+        view = get(self)
+        if value.data_ptr() != view.data_ptr():
+            view.copy_(value)
+    return property(get, put)
+
+
 class DeviceTables:
     """The five variables + optimizer slots as device buffers (reference model_utils.py:31-39)."""
 
@@ -285,8 +296,8 @@ class DeviceTables:
         TablesView, the plain kernels expect V col rows."""
         if d <= 0:
             raise ValueError("embedding size must be positive, got %d" % d)
-        if optimizer not in OPTIMIZER_CODES:
-            raise ValueError("optimizer must be one of %s (Keras names), got %r" % (", ".join(OPTIMIZER_CODES), optimizer))
+        if optimizer not in OPTIMIZERS:
+            raise ValueError("optimizer must be one of %s (Keras names), got %r" % (", ".join(OPTIMIZERS), optimizer))
         self.V, self.d_model, self.optimizer, self.device = int(V), int(d), optimizer, torch.device(device)
         self.V_row = int(V if V_row is None else V_row)
         self.V_col = int(V if V_col is None else V_col)
@@ -311,76 +322,28 @@ class DeviceTables:
         self._br, self._bc = uni(self.V_row), uni(self.V_col)
         self.R_ver = None           # uint8[V_row] once enable_twin() has doubled R and br (glove_tables.R_ver)
         self.R_tag = self.C_tag = None    # once enable_tags() has doubled both tables (glove_tables.R_tag)
-        self.scalars = torch.zeros(8, dtype=torch.float32, device=self.device)
+        spec = OPTIMIZERS[optimizer]                   # the slot layout and the scalars at step 0: the name's record
+        self.scalars = torch.tensor(spec.scalars, dtype=torch.float32, device=self.device)
         self.step = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.s1, self.s2 = {}, {}
         for n in self.NAMES:
             w = getattr(self, n)
-            if optimizer in ROW_WISE_OPTIMIZERS:       # one accumulator per row: float[rows] for R and C as for br and bc
-                self.s1[n] = torch.full((w.shape[0],), 0.1, dtype=torch.float32, device=self.device)
-            elif optimizer in ("Adagrad", "Ftrl"):
-                self.s1[n] = torch.full_like(w, 0.1)   # initial_accumulator_value (both optimizers' Keras default)
-            else:                                      # Adam / LazyAdam m / v, Adamax m / v, Adadelta accum_grad / accum_var; SGD momentum accumulator, RMSprop rms: zeros
-                self.s1[n] = torch.zeros_like(w)
-            if optimizer in ("Adam", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam"):
-                self.s2[n] = torch.zeros_like(w)       # (Ftrl: linear)
-        if optimizer in ("Adagrad", "Ftrl") + ROW_WISE_OPTIMIZERS:
-            self.scalars[1] = 0.1
-        if optimizer == "Nadam":
-            self.scalars[4:6] = 1.0                    # the momentum cache (Keras: an optimizer weight initialised to ones)
+            # (row-wise: one accumulator per row — float[rows] for R and C as for br and bc)
+            self.s1[n] = torch.full(w.shape[:1] if spec.row_wise else w.shape, spec.slot1_init, dtype=torch.float32, device=self.device)
+            if spec.slot2:
+                self.s2[n] = torch.zeros_like(w)
         self._struct = None
 
     # ---- the row table may be twinned (glove_tables.R_ver): R / br are the plain views [V_row, ...]; reading them
     # (or handing the tables to anything but the Adagrad step) first brings the table back to its plain form
-    @property
-    def R(self) -> torch.Tensor:
-        self.canonicalize()
-        return self._R[:self.V_row]
-
-    @R.setter
-    def R(self, value):                     # `tables.R += x` and `tables.R = tensor` write into the buffer the kernels see
-        view = self.R
-        if value.data_ptr() != view.data_ptr():
-            view.copy_(value)
-
-    @property
-    def br(self) -> torch.Tensor:
-        self.canonicalize()
-        return self._br[:self.V_row]
-
-    @br.setter
-    def br(self, value):
-        view = self.br
-        if value.data_ptr() != view.data_ptr():
-            view.copy_(value)
-
-    @property
-    def C(self) -> torch.Tensor:
-        self.canonicalize()
-        return self._C[:self.V_col]
-
-    @C.setter
-    def C(self, value):
-        view = self.C
-        if value.data_ptr() != view.data_ptr():
-            view.copy_(value)
-
-    @property
-    def bc(self) -> torch.Tensor:
-        self.canonicalize()
-        return self._bc[:self.V_col]
-
-    @bc.setter
-    def bc(self, value):
-        view = self.bc
-        if value.data_ptr() != view.data_ptr():
-            view.copy_(value)
+    R, br = _plain_view("R", "V_row"), _plain_view("br", "V_row")
+    C, bc = _plain_view("C", "V_col"), _plain_view("bc", "V_col")
 
     def enable_tags(self):
         """Second copies of BOTH tables + a step tag per row (glove_tables.R_tag / C_tag): what the tagged step
         (GLOVE_STEP_TAGGED) needs to read pre-step rows while it updates rows in the same launch.  For the latency-bound
         regime — small tables: costs (V_row + V) x d x 4 B of HBM."""
-        if self.R_tag is not None or self.optimizer not in ("Adagrad", "Adam") or self.R_ver is not None:
+        if self.R_tag is not None or not OPTIMIZERS[self.optimizer].tagged or self.R_ver is not None:
             return                               # (Adam: the twins flip as a whole every step — scalars[3] —, the tags stay zero)
         if self.V_col != self.V or 2 * max(self.V_row, self.V) * self.d * 4 >= 1 << 32:
             return                               # a sharded col table goes through views; 32-bit row offsets
@@ -397,13 +360,14 @@ class DeviceTables:
         """The policy: batches the library steps in the tagged form (at most TAGGED_STEP_MAX_BATCH pairs) on tables small enough
         that the step is a latency chain (both tables within the caches: 64 MB)."""
         small = batch_size <= TAGGED_STEP_MAX_BATCH and (self.V_row + self.V) * self.d * 4 <= (64 << 20)
-        if small and (self.optimizer == "Adagrad" or (self.optimizer == "Adam" and 2 * batch_size <= self.V_row + self.V)):
+        spec = OPTIMIZERS[self.optimizer]
+        if small and spec.tagged and (not spec.tagged_sweeps or 2 * batch_size <= self.V_row + self.V):
             self.enable_tags()
 
     def enable_twin(self):
         """Second copy of the row table + per-row version bytes: lets the fused step write a row's update beside the old
         row instead of through a partial-row slot (GLOVE_STEP_FUSED_TWIN).  Costs V_row x d x 4 B of HBM."""
-        if self.R_ver is not None or self.optimizer != "Adagrad" or self.R_tag is not None:
+        if self.R_ver is not None or not OPTIMIZERS[self.optimizer].twinned or self.R_tag is not None:
             return
         if 2 * self.V_row * self.d * 4 >= 1 << 32:
             return                               # 32-bit row offsets: the table cannot be doubled
@@ -426,7 +390,7 @@ class DeviceTables:
         # cache policy on tables the caches hold, the twin form also wins on the 61 MB table: V = 50 k, d = 300, B = 131,072
         # 96.2 -> 92.9 us per step, B = 65,536 64.9 -> 64.4, B = 1 M 295.0 -> 292.6: tools/ab_step_forms.py,
         # profiles/r05_exp_twin_form_on_cache_resident_tables.txt; below 32 MB nothing was measured: not enabled)
-        if self.optimizer == "Adagrad" and self.V_row * self.d * 4 >= (32 << 20):
+        if OPTIMIZERS[self.optimizer].twinned and self.V_row * self.d * 4 >= (32 << 20):
             self.enable_twin()
 
     def canonicalize(self):
@@ -830,9 +794,10 @@ def make_hyper(l2_reg=0.01, reg_mult=2.0, learning_rate=0.001, epsilon=1e-7, bet
     the touched-rows apply sweeps under Adam / RMSprop / Nadam (0 = `sides`) — see glove_hyper in the header."""
     h = GloveHyper()
     h.sides, h.head, h.neg_factor, h.step_form, h.sweep_sides = sides, head, neg_factor, step_form, sweep_sides
-    h.optimizer = OPTIMIZER_CODES[optimizer] if isinstance(optimizer, str) else int(optimizer)     # read by glove_step_sparse_f32 only
+    spec = OPTIMIZERS[optimizer] if isinstance(optimizer, str) else BY_CODE[int(optimizer)]     # (a name or its code)
+    h.optimizer = spec.code     # set here once: the wrappers hand the struct on as it is
     if rho is None:                     # the optimizer's own Keras default
-        rho = 0.95 if h.optimizer == OPTIMIZER_CODES["Adadelta"] else 0.9
+        rho = spec.rho
     h.momentum, h.nesterov, h.rho = momentum, int(bool(nesterov)), rho
     h.beta1, h.beta2 = beta1, beta2
     h.l2_reg, h.reg_mult, h.learning_rate, h.epsilon = l2_reg, reg_mult, learning_rate, epsilon
@@ -869,6 +834,15 @@ def _step_struct(tables, plans, hyper):
             tables._twin_dirty = True
             break
     return tables.struct(twin_ok=True)
+
+
+def _same_optimizer(tables, hyper):
+    """The record of `tables.optimizer`, for the entry points that take the optimizer from glove_hyper.optimizer: a hyper made
+    for another name would silently apply that one to these tables' slots."""
+    spec = OPTIMIZERS[tables.optimizer]
+    if hyper.optimizer != spec.code:
+        raise GloveHipError("%s tables, but the hyper names optimizer code %d: make_hyper(optimizer=...)" % (tables.optimizer, hyper.optimizer))
+    return spec
 
 
 class GloveHip:
@@ -990,48 +964,39 @@ class GloveHip:
                 block.plans[j].lent = (row_side, col_side)          # (keeps the epoch's arrays alive as long as the plan points at them)
 
     # ---- passes
+    def _plan_call(self, name, plan, tables, hyper, ws, *tail):
+        """An entry point of the shape (plan, tables, hyper, ws, ws_bytes, <tail>, stream), with the shared step workspace by default."""
+        ws = self.step_workspace(plan, tables.d) if ws is None else ws
+        _check(getattr(self.lib, name)(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper), _ptr(ws), ws.numel(),
+                                       *tail, _stream()), name)
+
     def passes(self, plan, tables, hyper, ws=None):
         """Both gather passes (row side and col side) in one launch."""
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_passes_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                         _ptr(ws), ws.numel(), _stream()), "glove_passes_f32")
+        self._plan_call("glove_passes_f32", plan, tables, hyper, ws)
 
     def rowpass(self, plan, tables, hyper, ws=None):
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_rowpass_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                          _ptr(ws), ws.numel(), _stream()), "glove_rowpass_f32")
+        self._plan_call("glove_rowpass_f32", plan, tables, hyper, ws)
 
     def colpass(self, plan, tables, hyper, ws=None):
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_colpass_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                          _ptr(ws), ws.numel(), _stream()), "glove_colpass_f32")
+        self._plan_call("glove_colpass_f32", plan, tables, hyper, ws)
 
     def rowside_step(self, plan, tables, hyper, ws=None):
         """The row side of a step, applied in place where a lane group holds an id completely (hyper.sides = 1); the
         col pass of the step must have run already: it gathers the old rows."""
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_rowside_step_adagrad_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                                       _ptr(ws), ws.numel(), _stream()), "glove_rowside_step_adagrad_f32")
+        self._plan_call("glove_rowside_step_adagrad_f32", plan, tables, hyper, ws)
 
     def rowside_step_opt(self, plan, tables, hyper, G_flat=None, ws=None):
         """The row side of a step under the optimizer `tables.optimizer` names (hyper.sides = 1; glove_rowside_step_f32).
-        G_flat: a dense gradient buffer of these tables (all zero between calls) — Adam, RMSprop and Nadam mark or sum the
-        row ids in it."""
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]
-        _check(self.lib.glove_rowside_step_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper), _ptr(ws),
-                                               ws.numel(), _ptr(G_flat), _stream()), "glove_rowside_step_f32")
+        G_flat: a dense gradient buffer of these tables (all zero between calls) — the names with a `row_scratch` in
+        trainer/optimizers.py mark or sum the row ids in it."""
+        _same_optimizer(tables, hyper)
+        self._plan_call("glove_rowside_step_f32", plan, tables, hyper, ws, _ptr(G_flat))
 
     def apply_adagrad(self, plan, tables, hyper, loss_out=None, ws=None):
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_apply_adagrad_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                                _ptr(ws), ws.numel(), _ptr(loss_out), _stream()),
-               "glove_apply_adagrad_f32")
+        self._plan_call("glove_apply_adagrad_f32", plan, tables, hyper, ws, _ptr(loss_out))
 
     def dense_grad(self, plan, tables, hyper, G_flat, ws=None):
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_dense_grad_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper),
-                                             _ptr(ws), ws.numel(), _ptr(G_flat), _stream()), "glove_dense_grad_f32")
+        self._plan_call("glove_dense_grad_f32", plan, tables, hyper, ws, _ptr(G_flat))
 
     def dense_adagrad(self, tables, hyper, G_flat, loss_out=None):
         _check(self.lib.glove_dense_adagrad_f32(C.byref(tables.struct()), C.byref(hyper), _ptr(G_flat),
@@ -1070,20 +1035,13 @@ class GloveHip:
 
     def pack_grad(self, plan, tables, hyper, packed: torch.Tensor, ws=None):
         """The plan's summed gradients (hyper.sides) as one packed list: packed is [capacity, d + 4] float32."""
-        _require(packed, torch.float32)
-        if packed.dim() != 2 or packed.shape[1] != tables.d + 4:
-            raise GloveHipError("packed buffer must be [entries, d + 4]")
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(self.lib.glove_pack_grad_f32(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper), _ptr(ws),
-                                            ws.numel(), _ptr(packed), packed.shape[0], _stream()), "glove_pack_grad_f32")
+        self._packing_call("glove_pack_grad_f32", plan, tables, hyper, packed, ws)
 
     def _packing_call(self, name, plan, tables, hyper, packed, ws):
         _require(packed, torch.float32)
         if packed.dim() != 2 or packed.shape[1] != tables.d + 4:
             raise GloveHipError("packed buffer must be [entries, d + 4]")
-        ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        _check(getattr(self.lib, name)(C.byref(plan.struct()), C.byref(tables.struct()), C.byref(hyper), _ptr(ws),
-                                       ws.numel(), _ptr(packed), packed.shape[0], _stream()), name)
+        self._plan_call(name, plan, tables, hyper, ws, _ptr(packed), packed.shape[0])
 
     def passes_packing(self, plan, tables, hyper, packed: torch.Tensor, ws=None):
         """The passes of hyper.sides; ids one lane group holds completely land in the packed list right away."""
@@ -1131,6 +1089,26 @@ class GloveHip:
                                               _stream()), "glove_gather_rows_f32")
 
     # ---- whole steps
+    def step(self, plan, tables, hyper, G_flat=None, loss_out=None, ws=None):
+        """One whole single-GPU step of `tables.optimizer` through the entry point its record names (trainer/optimizers.py).
+        G_flat: the dense gradient buffer of the names whose record says `step_buffer`."""
+        entry = OPTIMIZERS[tables.optimizer].entry
+        if entry == "adagrad":
+            self.step_adagrad(plan, tables, hyper, loss_out, ws)
+        else:
+            (self.step_adam if entry == "adam" else self.step_sparse)(plan, tables, hyper, G_flat, loss_out, ws)
+
+    def steps(self, plans, tables, hyper, G_flat=None, loss_out=None, ws=None):
+        """len(plans) consecutive steps: ONE host call where the name has a chained entry point, otherwise one call per plan."""
+        entry = OPTIMIZERS[tables.optimizer].entry
+        if entry == "adagrad":
+            self.steps_adagrad(plans, tables, hyper, loss_out, ws)
+        elif entry == "adam":
+            self.steps_adam(plans, tables, hyper, G_flat, loss_out, ws)
+        else:
+            for plan in plans:
+                self.step_sparse(plan, tables, hyper, G_flat, loss_out, ws)
+
     def step_adagrad(self, plan, tables, hyper, loss_out=None, ws=None):
         ws = self.step_workspace(plan, tables.d) if ws is None else ws
         _check(self.lib.glove_step_adagrad_f32(C.byref(plan.struct()), C.byref(_step_struct(tables, (plan,), hyper)), C.byref(hyper),
@@ -1156,11 +1134,12 @@ class GloveHip:
                "glove_step_adam_f32")
 
     def step_sparse(self, plan, tables, hyper, G_flat=None, loss_out=None, ws=None):
-        """One step under the Keras optimizer `tables.optimizer` names (glove_step_sparse_f32: SGD, RMSprop, Adamax, Adadelta, Ftrl, Nadam, LazyAdam, RowWiseAdagrad; Adagrad
-        and Adam go to their own entry points).  G_flat: the dense gradient buffer RMSprop, Nadam and Adam need."""
+        """One step under the optimizer `tables.optimizer` names (glove_step_sparse_f32 takes every name of trainer/optimizers.py;
+        inside the library those with an entry point of their own go there).  G_flat: the dense gradient buffer of the names
+        whose record says `step_buffer`.  `hyper` must have been made for the same name (make_hyper(optimizer=...))."""
         ws = self.step_workspace(plan, tables.d) if ws is None else ws
-        hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]
-        struct = _step_struct(tables, (plan,), hyper) if tables.optimizer in ("Adagrad", "Adam") else tables.struct()
+        spec = _same_optimizer(tables, hyper)
+        struct = _step_struct(tables, (plan,), hyper) if spec.chained else tables.struct()      # (own entry points: they know tagged / twinned tables)
         _check(self.lib.glove_step_sparse_f32(C.byref(plan.struct()), C.byref(struct), C.byref(hyper), _ptr(ws), ws.numel(),
                                               _ptr(G_flat), _ptr(loss_out), _stream()), "glove_step_sparse_f32")
 

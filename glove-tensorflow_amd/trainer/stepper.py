@@ -21,14 +21,18 @@ provider to exercise the sharding / collective logic with gloo on CPU.
 """
 from __future__ import annotations
 
+import logging
+
 import torch
+
+from trainer.hip_api import (FUSED_STEP_BYTES, RECORDS_AT_BUILD_MAX, DeviceTables, GloveHip, Pairs, PlanBlock, TablesView, _same_optimizer, auto_chunk_cap, make_hyper, staging_records)
+from trainer.optimizers import OPTIMIZERS, names
 
 
 class HipBackend:
     """Kernel provider on top of the C ABI (trainer.hip_api.GloveHip)."""
 
     def __init__(self, device):
-        from trainer.hip_api import GloveHip
         self.hip = GloveHip(device)
         self.device = torch.device(device)
         self.row_floats = None      # floats per table row, once the tables exist: lets resident plans carry what the fused step needs
@@ -41,38 +45,29 @@ class HipBackend:
                                    chunk_cap=chunk_cap, compact=True, d=self.row_floats, V_row=self.shard_rows,
                                    run_words=False if self.exchange else None)
 
-    def make_hyper(self, **kw):
-        from trainer.hip_api import make_hyper
-        return make_hyper(**kw)
+    make_hyper = staticmethod(make_hyper)
 
     def dense_grad_buffer(self, tables):
         return self.hip.dense_grad_buffer(tables)
 
-    def step_sparse_adagrad(self, plan, tables, hyper, loss_out):
-        if tables.optimizer == "Adagrad":
-            self.hip.step_adagrad(plan, tables, hyper, loss_out)
-        else:                                   # the other Keras names: passes + their apply epilogue (glove_step_sparse_f32)
-            self.hip.step_sparse(plan, tables, hyper, None, loss_out)
+    def step(self, plan, tables, hyper, G, loss_out):
+        """One whole single-GPU step of `tables.optimizer`.  G: its dense gradient buffer (step_buffer), None where it needs none."""
+        self.hip.step(plan, tables, hyper, G, loss_out)
 
-    def steps_sparse_adagrad(self, plans, tables, hyper, loss_out):
-        self.hip.steps_adagrad(plans, tables, hyper, loss_out)
-
-    def steps_dense_adam(self, plans, tables, hyper, G, loss_out):
-        self.hip.steps_adam(plans, tables, hyper, G, loss_out)
+    def steps(self, plans, tables, hyper, G, loss_out):
+        """Consecutive steps from one host call (optional in the protocol: a backend without it is stepped plan by plan)."""
+        self.hip.steps(plans, tables, hyper, G, loss_out)
 
     def local_dense_grad(self, plan, tables, hyper, G):
         self.hip.passes(plan, tables, hyper)
         self.hip.dense_grad(plan, tables, hyper, G)
 
     def apply_dense(self, tables, hyper, G, loss_out):
-        if tables.optimizer == "Adagrad":
-            self.hip.dense_adagrad(tables, hyper, G, loss_out)
-        elif tables.optimizer in ("Adam", "RMSprop"):    # the dense-decay optimizers: every row's slots move every step
-            from trainer.hip_api import OPTIMIZER_CODES
-            hyper.optimizer = OPTIMIZER_CODES[tables.optimizer]
-            self.hip.dense_adam(tables, hyper, G, loss_out)
-        else:
+        apply = OPTIMIZERS[tables.optimizer].dense_apply     # dense_adagrad, or dense_adam for the dense-decay names (every row's slots move every step)
+        if apply is None:
             raise ValueError("no dense apply for %s" % tables.optimizer)
+        _same_optimizer(tables, hyper)          # (glove_dense_adam_f32 takes the sweep from glove_hyper.optimizer)
+        getattr(self.hip, apply)(tables, hyper, G, loss_out)
 
     # ---- pieces of the row-sharded step (hyper.sides selects the side)
     def passes(self, plan, tables, hyper):
@@ -88,14 +83,15 @@ class HipBackend:
         """G (the other Keras names): a dense gradient buffer of `tables` whose row half is zero between steps — the step's
         scratch (glove_rowside_step_f32: Adam and Nadam mark the row ids in its first V_row floats, RMSprop sums the row
         gradients into its row half, all zero again afterwards).  None: the backend keeps the least scratch that serves."""
-        if tables.optimizer == "Adagrad":
+        spec = OPTIMIZERS[tables.optimizer]
+        if spec.own_rowside:                    # its own entry point, applied in place (glove_rowside_step_adagrad_f32)
             self.hip.rowside_step(plan, tables, hyper)
             return
-        if G is None and tables.optimizer in ("Adam", "RMSprop", "Nadam"):
+        if G is None and spec.row_scratch is not None:
             key = (tables.optimizer, tables.V_row, tables.d)
             G = self._row_G.get(key)
             if G is None:
-                n = self.hip.grad_layout(tables)["G_C"] if tables.optimizer == "RMSprop" else tables.V_row
+                n = self.hip.grad_layout(tables)["G_C"] if spec.row_scratch == "row_half" else tables.V_row
                 G = self._row_G[key] = torch.zeros(n, dtype=torch.float32, device=tables.device)
         self.hip.rowside_step_opt(plan, tables, hyper, G)
 
@@ -159,7 +155,6 @@ class HipBackend:
     def col_view(self, tables, bufs, capacity: int):
         """The tables the passes of one batch see: this rank's row shard and, as the col table, the fetched rows
         (compact col ids index it); the col side's slots are never touched through this view."""
-        from trainer.hip_api import TablesView
         return TablesView(tables, C=bufs["C"], bc=bufs["bc"], s1_C=bufs["C"], s1_bc=bufs["bc"],
                           V=max(capacity, tables.V_row), V_row=tables.V_row)
 
@@ -167,7 +162,6 @@ class HipBackend:
         """The owner's half of the col side: `recv` holds, rank after rank, the summed gradient rows the ranks computed
         for this rank's col rows `ids` (owner-local indices); they are added in rank order and the optimizer is applied.
         Under Adam, RMSprop and Nadam every other row of the shard takes its G = 0 update (the sweep of side 0 only)."""
-        from trainer.hip_api import TablesView
         if "view" not in state:
             f32 = dict(dtype=torch.float32, device=tables.device)
             dummy, dummy_b = torch.zeros(4, tables.d, **f32), torch.zeros(4, **f32)
@@ -303,7 +297,6 @@ class GraphedSteps:
             except Exception as exc:             # a transport that refuses capture: the same launches, eagerly, from now on
                 if not self._multi:
                     raise
-                import logging
                 logging.getLogger(__name__).warning("hipGraph capture of the multi-rank step failed (%s: %s): launching eagerly",
                                                     type(exc).__name__, exc)
                 torch.cuda.synchronize()
@@ -333,6 +326,11 @@ class GraphedSteps:
         for _, fn in self.phases():
             fn(item)
 
+    def read_loss(self) -> dict:
+        """Host read of the last step's scalars (synchronises; call at the logging cadence only)."""
+        loss, L, reg, _ = self.loss_out.tolist()
+        return {"loss": loss, "weighted_mse": L, "regularization_loss": reg}
+
     def release_graphs(self):
         """Drops the captured steps.  Call before torch.distributed.destroy_process_group(): RCCL does not finish tearing a
         communicator down while hipGraphs that captured its collectives exist (the call hangs)."""
@@ -351,16 +349,13 @@ class GraphedSteps:
 class Stepper(GraphedSteps):
     """`exchange`: "dense" = all-reduce of the flat dense gradient buffer; "rows" = all-gather of packed touched-row
     lists; "auto" = rows when `prepare(plans)` finds the ranks' lists together shorter than the dense buffer, else dense.
-    Which optimizers (`tf.keras.optimizers.get`, reference train_utils.py:13-16) run on several ranks, and how:
-    Adagrad either way; the per-row ones (SGD, Adamax, Adadelta, Ftrl: only touched rows move) on the touched-rows
-    exchange, whose apply takes their epilogue; the dense-decay ones (Adam, RMSprop: every row's slots move every step) on
-    the dense all-reduce.  Nadam (m, v decay everywhere, touched rows move) rides the touched-rows exchange too: the lists
-    ARE the union of the ranks' ids — the rows no list names decay (a sweep in front of the apply), the named ones move.
-    LazyAdam (this build's addition, not a Keras name: Adam on the touched rows alone) is one of the per-row ones, and so is
-    RowWiseAdagrad (one Adagrad accumulator per embedding row: its table slots are float[rows], nothing a dense sweep could walk)."""
+    Which optimizers (`tf.keras.optimizers.get`, reference train_utils.py:13-16, and this build's additions) run on several
+    ranks, and how, is the `exchange` of their record in trainer/optimizers.py: "either"; "rows" for the per-row ones (only
+    touched rows move), whose epilogue the touched-rows apply takes; "dense" for the dense-decay ones (every row's slots
+    move every step), which ride the dense all-reduce."""
 
-    ROWS_ONLY = ("SGD", "Adamax", "Adadelta", "Ftrl", "Nadam", "LazyAdam", "RowWiseAdagrad")       # touched-rows exchange (the lists carry the union of the ids)
-    DENSE_ONLY = ("Adam", "RMSprop")                        # dense-decay optimizers: dense all-reduce
+    ROWS_ONLY = names(lambda o: o.exchange == "rows")       # touched-rows exchange (the lists carry the union of the ids)
+    DENSE_ONLY = names(lambda o: o.exchange == "dense")     # dense-decay optimizers: dense all-reduce
 
     def __init__(self, backend, tables, hyper_kwargs: dict, batch_size: int, world=1, dist=None, exchange="auto",
                  collectives=False):
@@ -371,34 +366,26 @@ class Stepper(GraphedSteps):
             backend.exchange = True         # plans built from here on keep chunk records (the packing passes read them)
         if self._multi and dist is None:
             raise ValueError("world > 1 needs an initialised torch.distributed module")
-        if exchange not in ("auto", "dense", "rows"):
-            raise ValueError("exchange must be auto, dense or rows")
         if exchange == "rows" and tables.optimizer in self.DENSE_ONLY:
             raise ValueError("the touched-rows exchange is for optimizers that move touched rows only (Keras' %s moves every row "
                              "every step)" % tables.optimizer)
-        if exchange == "dense" and self._multi and tables.optimizer in self.ROWS_ONLY:
-            raise ValueError("%s runs on the touched-rows exchange (its dense form would need the ranks' id marks)" % tables.optimizer)
-        if self._multi and tables.optimizer not in ("Adagrad",) + self.ROWS_ONLY + self.DENSE_ONLY:
-            raise ValueError("the data-parallel form takes the eight Keras names (Adagrad, SGD, Adamax, Adadelta, Ftrl, Nadam, Adam, RMSprop), LazyAdam and RowWiseAdagrad, got %s" % tables.optimizer)
-        if self._multi and tables.optimizer in self.ROWS_ONLY:
-            exchange = "rows"
-        self.hyper = backend.make_hyper(batch_size=batch_size * self.world, **hyper_kwargs)
+        exchange = sharded_exchange(tables, exchange, self._multi, "the data-parallel form takes")     # (the names, the exchange's spelling, "rows" for the names that need the lists)
+        spec = OPTIMIZERS[tables.optimizer]
+        self.hyper = backend.make_hyper(batch_size=batch_size * self.world, **dict(hyper_kwargs, optimizer=tables.optimizer))
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=tables.device)
-        # Adam (dense whole-table decay) and every multi-rank step go through the dense buffer; RMSprop (whole-slot decay) too,
-        # inside its own entry point
-        self.dense = self._multi or tables.optimizer == "Adam"
-        self._rms_G = backend.dense_grad_buffer(tables) if tables.optimizer in ("RMSprop", "Nadam") and not self._multi else None
+        # every multi-rank step goes through the dense buffer, and so does one rank's step of a `dense_step` name (Adam: dense
+        # whole-table decay); other names that need the buffer (RMSprop: whole-slot decay) use it inside their own entry point
+        self.dense = self._multi or spec.dense_step
         form = int(hyper_kwargs.get("step_form", 0) or 0)
-        if not self.dense and hasattr(tables, "maybe_enable_twin"):
+        if not self._multi and hasattr(tables, "maybe_enable_twin"):     # (each a no-op under a name without such a form)
             if form in (0, 5):
-                tables.maybe_enable_tags(batch_size)   # small batches on small tables: the tagged step
+                tables.maybe_enable_tags(batch_size)   # small batches on small tables: the tagged step (Adam: its one-launch step, step_many)
             if form in (0, 4):
                 tables.maybe_enable_twin()      # big tables: the fused step writes new rows beside the old ones
-        elif not self._multi and tables.optimizer == "Adam" and form in (0, 5) and hasattr(tables, "maybe_enable_tags"):
-            tables.maybe_enable_tags(batch_size)   # small batches on small tables: Adam's one-launch step on twinned tables
-        self.G = backend.dense_grad_buffer(tables) if self.dense else None
+        # the buffer the ranks exchange; on one rank the step's own, where its name needs one (None otherwise)
+        self.G = backend.dense_grad_buffer(tables) if self._multi else step_buffer(backend, tables)
         self.exchange, self.rows, self.bufs = exchange, False, None
-        self.payload_floats = int(self.G.numel()) if self.G is not None else 0
+        self.payload_floats = int(self.G.numel()) if self.dense else 0
 
     def prepare(self, plans=None, force_world=None, batch_size=None):
         """Agree (collectively) on the exchange.  Static stream: from the id counts of every rank's resident plans.
@@ -408,8 +395,8 @@ class Stepper(GraphedSteps):
         if self.tables.optimizer in self.DENSE_ONLY or self.exchange == "dense" or (
                 world == 1 and not self._multi and self.exchange != "rows"):
             return
-        if self.G is None:
-            self.G, self.dense = self.backend.dense_grad_buffer(self.tables), True
+        if not self.dense:
+            self.G, self.dense = self.backend.dense_grad_buffer(self.tables) if self.G is None else self.G, True
         if plans is None:
             most = min(int(batch_size), self.tables.V_row) + min(int(batch_size), self.tables.V)
         else:
@@ -429,9 +416,7 @@ class Stepper(GraphedSteps):
         """The step as named pieces [(name, fn(plan))]: what step() runs, in order (bench.py times them apart)."""
         b, t, h = self.backend, self.tables, self.hyper
         if not self.dense:
-            if self._rms_G is not None:
-                return [("step", lambda p: b.hip.step_sparse(p, t, h, self._rms_G, self.loss_out))]
-            return [("step", lambda p: b.step_sparse_adagrad(p, t, h, self.loss_out))]
+            return plain_step_phases(b, t, h, self.loss_out, self.G)
         if self.rows:
             ph = [("passes", lambda p: b.passes_packing(p, t, h, self.bufs["send"])),
                   ("pack_grad", lambda p: b.pack_rest(p, t, h, self.bufs["send"]))]
@@ -441,6 +426,7 @@ class Stepper(GraphedSteps):
                 ph.append(("all_gather", lambda p: self.bufs["recv"][0].copy_(self.bufs["send"])))
             ph.append(("combine_apply", lambda p: b.apply_gathered(self.bufs, self.world, t, h, self.G, self.loss_out)))
             return ph
+        # (deliberate: one rank's Adam lands here too — passes, dense_grad, dense_apply —, not in its one-call entry point)
         ph = [("passes", lambda p: b.passes(p, t, h)), ("dense_grad", lambda p: b.dense_grad(p, t, h, self.G))]
         if self._multi:
             ph.append(("all_reduce", lambda p: self.dist.all_reduce(self.G)))     # sum over ranks; the tail carries the loss partials
@@ -448,19 +434,20 @@ class Stepper(GraphedSteps):
         return ph
 
     def step_many(self, plans):
-        """Several consecutive steps; on one GPU they are issued by one C call."""
-        if not self.dense and self.tables.optimizer == "Adagrad" and hasattr(self.backend, "steps_sparse_adagrad"):
-            self.backend.steps_sparse_adagrad(plans, self.tables, self.hyper, self.loss_out)
-        elif (not self._multi and self.tables.optimizer == "Adam" and not self.rows and hasattr(self.backend, "steps_dense_adam")):
-            self.backend.steps_dense_adam(plans, self.tables, self.hyper, self.G, self.loss_out)
+        """Several consecutive steps; on one GPU, under a name with a chained entry point, they are issued by one C call."""
+        spec = OPTIMIZERS[self.tables.optimizer]
+        steps = getattr(self.backend, "steps", None)        # (optional in the protocol: the test backends have none)
+        plain = not self._multi and not self.rows and self.dense == spec.dense_step      # still the name's own one-rank form: nobody forced the exchange's path
+        if plain and spec.chained and steps is not None:    # (deliberate: Adam's chained entry point here, the dense phases in step())
+            steps(plans, self.tables, self.hyper, self.G, self.loss_out)
         else:
             for plan in plans:
                 self.step(plan)
 
-    def read_loss(self) -> dict:
-        """Host read of the last step's scalars (synchronises; call at the logging cadence only)."""
-        loss, L, reg, _ = self.loss_out.tolist()
-        return {"loss": loss, "weighted_mse": L, "regularization_loss": reg}
+    @property
+    def _rms_G(self):
+        """The one-rank step's own dense buffer under a name that is not stepped through the dense phases (read by tests)."""
+        return None if self.dense else self.G
 
 
 def owned_rows(V: int, world: int, rank: int) -> int:
@@ -492,31 +479,31 @@ def route_by_row_owner(coo: dict, world: int, rank: int, dist) -> dict:
     return out
 
 
-KERAS_OPTIMIZERS = ("Adagrad", "SGD", "RMSprop", "Adamax", "Adam", "Adadelta", "Ftrl", "Nadam")
-SHARDED_OPTIMIZERS = KERAS_OPTIMIZERS + ("LazyAdam", "RowWiseAdagrad")       # what the sharded forms take: both additions ride the lists like Adamax
+KERAS_OPTIMIZERS = names(lambda o: o.keras)
+SHARDED_OPTIMIZERS = KERAS_OPTIMIZERS + names(lambda o: not o.keras)       # what the multi-rank forms take: this build's additions ride the lists like Adamax
+
+
+def step_buffer(backend, tables):
+    """The dense gradient buffer the single-GPU step of `tables.optimizer` needs (all zero between steps), or None.
+    `backend`: anything with dense_grad_buffer(tables) — a kernel provider or GloveHip itself."""
+    return backend.dense_grad_buffer(tables) if OPTIMIZERS[tables.optimizer].step_buffer else None
 
 
 def plain_step_phases(backend, tables, hyper, loss_out, G):
     """The single-GPU step of `tables.optimizer` as Stepper runs it on one rank, as [(name, fn(plan))]: a sharded form alone in
-    the world takes exactly these launches.  G: the dense gradient buffer of Adam, RMSprop and Nadam (plain_step_buffer)."""
+    the world takes exactly these launches.  G: step_buffer(backend, tables)."""
     b, t, h = backend, tables, hyper
-    if t.optimizer == "Adam":
+    if OPTIMIZERS[t.optimizer].dense_step:      # (deliberate: Adam as three phases, not its one-call entry point)
         return [("passes", lambda p: b.passes(p, t, h)), ("dense_grad", lambda p: b.dense_grad(p, t, h, G)),
                 ("dense_apply", lambda p: b.apply_dense(t, h, G, loss_out))]
-    if t.optimizer in ("RMSprop", "Nadam") and hasattr(b, "hip"):
-        return [("step", lambda p: b.hip.step_sparse(p, t, h, G, loss_out))]
-    return [("step", lambda p: b.step_sparse_adagrad(p, t, h, loss_out))]
+    return [("step", lambda p: b.step(p, t, h, G, loss_out))]
 
 
-def plain_step_buffer(backend, tables):
-    return backend.dense_grad_buffer(tables) if tables.optimizer in ("Adam", "RMSprop", "Nadam") else None
-
-
-def sharded_exchange(tables, exchange: str, multi: bool) -> str:
-    """The col-side exchange a row-sharded form takes for `tables.optimizer`: the per-row optimizers and Nadam (only
-    touched rows move) need the lists — the union of the ranks' ids —, Adagrad, Adam and RMSprop take either."""
+def sharded_exchange(tables, exchange: str, multi: bool, who="the sharded forms take") -> str:
+    """The exchange a multi-rank form (data parallel; row-sharded: its col side) takes for `tables.optimizer`: the names whose
+    record says "rows" (only touched rows move) need the lists — the union of the ranks' ids —, the others take what is asked."""
     if tables.optimizer not in SHARDED_OPTIMIZERS:
-        raise ValueError("the sharded forms take the eight Keras names (%s), LazyAdam and RowWiseAdagrad, got %s" % (", ".join(KERAS_OPTIMIZERS), tables.optimizer))
+        raise ValueError("%s the eight Keras names (%s), %s, got %s" % (who, ", ".join(KERAS_OPTIMIZERS), " and ".join(SHARDED_OPTIMIZERS[len(KERAS_OPTIMIZERS):]), tables.optimizer))
     if exchange not in ("auto", "dense", "rows"):
         raise ValueError("exchange must be auto, dense or rows")
     if multi and tables.optimizer in Stepper.ROWS_ONLY:
@@ -541,7 +528,7 @@ class RowShardedStepper(GraphedSteps):
 
     With inv_batch = 1 / (world * B) the result equals a single-GPU step on the union of the ranks'
     batches (tests/test_dp_gloo.py).  On one rank nothing is exchanged and the step is the plain single-GPU one.
-    All eight Keras names: the per-row ones and Nadam take the lists' exchange, Adagrad, Adam and RMSprop either."""
+    Every name of trainer/optimizers.py (sharded_exchange says which col-side exchange a name takes)."""
 
     def __init__(self, backend, tables, hyper_kwargs: dict, batch_size: int, world: int, dist, exchange="auto",
                  collectives=False):
@@ -558,7 +545,7 @@ class RowShardedStepper(GraphedSteps):
         self.loss_out = torch.zeros(4, dtype=torch.float32, device=tables.device)
         self.tail = torch.zeros(4, dtype=getattr(backend, "tail_dtype", torch.float32), device=tables.device)   # loss partials over the ranks
         self._gather = SideCollective(tables.device)        # the lists' all-gather while it is in flight
-        self.G = backend.dense_grad_buffer(tables) if self._multi else plain_step_buffer(backend, tables)
+        self.G = backend.dense_grad_buffer(tables) if self._multi else step_buffer(backend, tables)
         self.exchange, self.rows, self.bufs = exchange, False, None
         self.payload_floats = int(backend.col_half(tables, self.G).numel()) if self._multi else 0
 
@@ -587,7 +574,7 @@ class RowShardedStepper(GraphedSteps):
             ph = [("colpass", lambda p: b.passes_packing(p, t, self.hyper_cols, self.bufs["send"]))]
         else:
             ph = [("colpass", lambda p: b.colpass(p, t, self.hyper_cols))]
-        if t.optimizer == "Adagrad":
+        if OPTIMIZERS[t.optimizer].own_rowside:
             rowside = lambda p: b.rowside_step(p, t, self.hyper_rows)
         else:   # the row half of self.G is zero between steps (the col exchange uses the col half): the row side's scratch
             rowside = lambda p: b.rowside_step(p, t, self.hyper_rows, self.G)
@@ -624,10 +611,6 @@ class RowShardedStepper(GraphedSteps):
         for plan in plans:
             self.step(plan)
 
-    def read_loss(self) -> dict:
-        loss, L, reg, _ = self.loss_out.tolist()
-        return {"loss": loss, "weighted_mse": L, "regularization_loss": reg}
-
 
 class ShardedStepper(GraphedSteps):
     """BASELINE config 5 with BOTH tables sharded ("row-embedding table sharded across 8 GPUs with all-to-all token-id
@@ -658,13 +641,12 @@ class ShardedStepper(GraphedSteps):
         hyper_kwargs = dict(hyper_kwargs, optimizer=tables.optimizer)
         self.backend, self.tables, self.world, self.rank, self.dist = backend, tables, int(world), int(rank), dist
         self._multi = self.world > 1 or bool(collectives)      # collectives: the transport even with one rank (tests)
-        if self._multi and hasattr(backend, "exchange"):
-            backend.exchange = True         # plans built from here on keep chunk records (the packing passes read them)
         self.local_only = self.world == 1 and not exercise_exchange
         self.col_per = 0        # > 0: the col ids handed in are numbered owner-major, ceil(V / world) per owner (the runner sets it from its stream)
         if hasattr(backend, "exchange"):
-            backend.exchange = not self.local_only      # (alone in the world the step is the plain one: run words will do)
-        if self.local_only and tables.optimizer == "Adagrad" and hasattr(tables, "maybe_enable_twin"):
+            # plans built from here on keep chunk records (the packing passes read them); alone in the world the step is the plain one: run words will do
+            backend.exchange = not self.local_only
+        if self.local_only and hasattr(tables, "maybe_enable_twin"):
             tables.maybe_enable_twin()
         gb = batch_size * self.world
         self.hyper = backend.make_hyper(batch_size=gb, **hyper_kwargs)
@@ -676,7 +658,7 @@ class ShardedStepper(GraphedSteps):
         self._push = SideCollective(tables.device)          # the col gradients' all-to-all while it is in flight
         self._prep_pg = None                                # the communicator of the prepare's collectives (prepare_group)
         self._spare = {}                                    # staging plans of dropped batches, by (B, id bound, chunk cap)
-        self.G = plain_step_buffer(backend, tables) if self.local_only else None     # (alone in the world: the plain step's)
+        self.G = step_buffer(backend, tables) if self.local_only else None     # (alone in the world: the plain step's)
         if hasattr(backend, "shard_rows"):
             backend.shard_rows = tables.V_row       # local row ids: anything outside the shard counts as id 0, like a bad col id
 
@@ -742,7 +724,6 @@ class ShardedStepper(GraphedSteps):
         (ReshufflingRunner._prepare_one): by the time it reads, the copy has long landed, and the host never waits for a
         prepare launch queued behind the running step's kernels (six such waits per batch made a prepare 1.7 ms beside
         1.3 ms steps: the host fell behind and the steps waited for their fetch lists at every epoch's end).  Collective."""
-        from trainer.hip_api import Pairs, PlanBlock, auto_chunk_cap
         hip, W, dist, per = self.backend.hip, self.world, self.dist, self.col_per
         pg = self.prepare_group()
         sl = slice(first, first + B)
@@ -915,10 +896,6 @@ class ShardedStepper(GraphedSteps):
         """Waits for the collective a phase started (for callers that time the phases one by one)."""
         self._push.wait()
 
-    def read_loss(self) -> dict:
-        loss, L, reg, _ = self.loss_out.tolist()
-        return {"loss": loss, "weighted_mse": L, "regularization_loss": reg}
-
 
 class ReshufflingRunner:
     """Training over a stream whose pairs are re-permuted every epoch (`--epoch-shuffle full`, the reference's
@@ -955,7 +932,6 @@ class ReshufflingRunner:
         120 / 117; C4 674 / 687), True / False force it."""
         if graphs is None:
             graphs = stream.B <= self.GRAPH_MAX_BATCH
-        from trainer.hip_api import auto_chunk_cap
         self.hip, self.stream, self.tables, self.hyper, self.stepper = hip, stream, tables, hyper, stepper
         self.cap = chunk_cap or auto_chunk_cap(stream.B, stream.V, tables.d)
         self.burst = max(1, int(burst))
@@ -995,15 +971,14 @@ class ReshufflingRunner:
         # the library takes a fused step (big batches on big tables, one GPU, Adagrad: it judges a device-refilled plan by the
         # most ids its batch can hold) or where the chunks are reasonably filled (the rule of Plan.compact); otherwise pair
         # arrays of their own.  A plan with records keeps no pair arrays: the records hold the pair fields.
-        from trainer.hip_api import FUSED_STEP_BYTES, PlanBlock, staging_records
         form = getattr(hyper, "step_form", 0)
         probe = hip.build_plan(*(t.contiguous() for t in stream.batch(0)), V, chunk_cap=self.cap, V_row=shard_rows, links=False)
         counts = probe.counts.tolist()
         del probe
-        fused = single and tables.optimizer == "Adagrad" and (
+        spec = OPTIMIZERS[tables.optimizer]
+        fused = single and spec.twinned and (
             form in (2, 3, 4) or (form == 0 and bool(staging_records(B, tables.V_row, V, tables.d)) and
                                   (counts[1] + counts[3]) * tables.d * 16 >= FUSED_STEP_BYTES))
-        from trainer.hip_api import RECORDS_AT_BUILD_MAX
         records = fused or B <= RECORDS_AT_BUILD_MAX or 4 * B >= self.cap * max(counts[0], counts[2], 1)
         if fused and form == 0 and hasattr(tables, "maybe_enable_twin"):
             tables.maybe_enable_twin()      # as Stepper does: the fused step writes new rows beside the old ones
@@ -1013,7 +988,7 @@ class ReshufflingRunner:
         if self.run_words:
             records = False
         self.records = records
-        if single and records and tables.optimizer in ("Adagrad", "Adam") and form in (0, 5) and hasattr(tables, "maybe_enable_tags"):
+        if single and records and spec.tagged and form in (0, 5) and hasattr(tables, "maybe_enable_tags"):
             tables.maybe_enable_tags(B)     # small batches on small tables: the tagged step (one launch for all the row work)
         # ... and the pair fields are not even copied: the plans point into the epoch's arrays (the steps are issued by C calls
         # here, not replayed from graphs that would hold last epoch's addresses); a deal then waits for the steps that read
@@ -1031,7 +1006,7 @@ class ReshufflingRunner:
         self.slots = [PlanBlock(plans[:self.S]), PlanBlock(plans[self.S:])]
         self.sorted_ws = torch.empty(max(hip.lib.glove_plan_sorted_workspace_bytes(B, self.S), 256), dtype=torch.uint8, device=dev)
         self.step_ws = torch.empty(hip.lib.glove_step_workspace_bytes(B, first.cap_chunks, tables.d), dtype=torch.uint8, device=dev)
-        self.G = hip.dense_grad_buffer(tables) if single and tables.optimizer in ("Adam", "RMSprop", "Nadam") else None
+        self.G = step_buffer(hip, tables) if single else None
         # ---- segments: `_g` = the segment the next step belongs to (counted over all epochs), slot = segment % 2
         self._g, self._issued, self._entered = 0, 0, -1
         self._cursor = (stream.epoch, 0)       # (epoch, segment of the epoch) the next build takes
@@ -1043,7 +1018,6 @@ class ReshufflingRunner:
         self.host_counts = single and not self.graphs_on
         self._issue_build()                    # segment 0: needed now anyway
         # every kernel (and collective) of a step runs once outside any capture, on throw-away tables of the same shape
-        from trainer.hip_api import DeviceTables
         real = self.tables
         scratch = DeviceTables(real.V, real.d_model, real.optimizer, device=dev, seed=0, V_row=real.V_row)
         if getattr(real, "R_ver", None) is not None:
@@ -1071,12 +1045,8 @@ class ReshufflingRunner:
     def _step(self, plan):
         if self.stepper is not None:
             self.stepper.step(plan)
-        elif self.tables.optimizer == "Adagrad":
-            self.hip.step_adagrad(plan, self.tables, self.hyper, self.loss_out, self.step_ws)
-        elif self.tables.optimizer == "Adam":
-            self.hip.step_adam(plan, self.tables, self.hyper, self.G, self.loss_out, self.step_ws)
-        else:                                   # the other Keras names (glove_step_sparse_f32)
-            self.hip.step_sparse(plan, self.tables, self.hyper, self.G, self.loss_out, self.step_ws)
+        else:       # (deliberate: under Adam this is glove_step_adam_f32, not the three dense phases of Stepper.step)
+            self.hip.step(plan, self.tables, self.hyper, self.G, self.loss_out, self.step_ws)
 
     def _segments_per_epoch(self) -> int:
         return (self.nb + self.S - 1) // self.S
@@ -1173,7 +1143,6 @@ class ReshufflingRunner:
             except Exception as exc:                # a transport that refuses capture: the same launches, eagerly, from now on
                 if self.stepper is None:
                     raise
-                import logging
                 logging.getLogger(__name__).warning("hipGraph capture of the multi-rank step failed (%s: %s): launching eagerly",
                                                     type(exc).__name__, exc)
                 torch.cuda.synchronize()
@@ -1186,15 +1155,13 @@ class ReshufflingRunner:
         self._steps(plans[off:off + count])
 
     def _steps(self, plans):
-        """Consecutive steps.  One GPU, Adagrad: one host call (on step-tagged tables the library chains them: one launch per
-        step, the global bias handed on through the workspace)."""
-        if self.stepper is None and self.tables.optimizer == "Adagrad":
-            self.hip.steps_adagrad(plans, self.tables, self.hyper, self.loss_out, ws=self.step_ws)
-        elif self.stepper is None and self.tables.optimizer == "Adam":
-            self.hip.steps_adam(plans, self.tables, self.hyper, self.G, self.loss_out, ws=self.step_ws)
+        """Consecutive steps.  One GPU, a name with a chained entry point: one host call (on step-tagged tables the library
+        chains them: one launch per step, the global bias handed on through the workspace)."""
+        if self.stepper is None:
+            self.hip.steps(plans, self.tables, self.hyper, self.G, self.loss_out, self.step_ws)
         else:
             for plan in plans:
-                self._step(plan)
+                self.stepper.step(plan)
 
     def run(self, n_steps: int) -> int:
         """Up to `n_steps` steps, never across a segment's or the epoch's end; returns the number done (the caller asks again)."""

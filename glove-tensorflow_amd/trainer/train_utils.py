@@ -15,25 +15,13 @@ import time
 
 import torch
 
+from trainer.optimizers import OPTIMIZERS as _TABLE
+
 logger = logging.getLogger(__name__)
 EVAL_INTERVAL = 300
 
-# Keras-legacy defaults of the optimizers the HIP path implements
-OPTIMIZERS = {
-    "Adagrad": {"initial_accumulator_value": 0.1, "epsilon": 1e-7},
-    "Adam": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},
-    # not a Keras-legacy name: Adam that moves only the rows a batch touches (include/glove_hip.h GLOVE_OPT_LAZYADAM)
-    "LazyAdam": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},
-    # not a Keras-legacy name either: Adagrad with ONE accumulator per embedding row (include/glove_hip.h GLOVE_OPT_ROWWISE_ADAGRAD)
-    "RowWiseAdagrad": {"initial_accumulator_value": 0.1, "epsilon": 1e-7},
-    "SGD": {"momentum": 0.0, "nesterov": False},
-    "RMSprop": {"rho": 0.9, "momentum": 0.0, "epsilon": 1e-7, "centered": False},
-    "Adamax": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7},
-    "Nadam": {"beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7, "schedule_decay": 0.004},
-    "Adadelta": {"rho": 0.95, "epsilon": 1e-7},
-    "Ftrl": {"learning_rate_power": -0.5, "initial_accumulator_value": 0.1, "l1_regularization_strength": 0.0,
-             "l2_regularization_strength": 0.0, "l2_shrinkage_regularization_strength": 0.0, "beta": 0.0},
-}
+# Keras-legacy defaults of the optimizers the HIP path implements (trainer/optimizers.py)
+OPTIMIZERS = {o.name: dict(o.defaults) for o in _TABLE.values()}
 
 
 def get_optimizer(optimizer_name="Adam", **kwargs) -> dict:

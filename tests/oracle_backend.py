@@ -107,7 +107,7 @@ class OracleBackend:
         ref.apply_update(t, gr, hp)
         G.zero_()
 
-    def step_sparse_adagrad(self, plan, tables, hyper, loss_out):
+    def step(self, plan, tables, hyper, G, loss_out):            # (G, the dense buffer some names' device step needs, is ignored)
         row, col, w, y = plan
         loss, L, reg = ref.train_step(tables.t, row, col, w, y, hyper["hp"])
         loss_out[0], loss_out[1], loss_out[2] = loss, L, reg

@@ -8,7 +8,7 @@ from sharded_oracle_backend import ShardedOracleBackend
 
 
 class RowWiseOracleBackend(ShardedOracleBackend):
-    def step_sparse_adagrad(self, plan, tables, hyper, loss_out):
+    def step(self, plan, tables, hyper, G, loss_out):
         loss_out[0], loss_out[1], loss_out[2] = rw.train_step(tables.t, *plan, hyper["hp"])
 
     def rowside_step(self, plan, tables, hyper, G=None):

@@ -7,6 +7,7 @@ one-launch (tagged) Adagrad and Adam steps on a dealt batch that holds a heavy i
   A  every kernel shape            B  heavy ids (the workgroup path)   C  edge shapes
   D  mid-run state, large step     E  device-refilled plans            F  touched-rows exchange on one GPU
   G  tagged form on a dealt heavy batch (Adagrad, Adam)
+  H  GloveHip.step == the name's own wrapper, bit for bit (every name)
 
 Tolerances (those of test_gpu_optimizers.py): loss rtol 2e-5; one step rtol 1e-5 / atol 1e-6; trajectories 5e-5 / 5e-6.
 In every case the padding columns of R and C stay exactly zero, those of every slot at their initial value, global_step
@@ -347,3 +348,61 @@ def test_g_tagged_form_on_a_dealt_heavy_batch(hip, optimizer):
             if n_ in dt.s2:
                 assert torch.equal(runs[0][0].s2[n_], dt.s2[n_]), "slot2 " + n_
         assert torch.equal(runs[0][0].scalars[:3], dt.scalars[:3]) and runs[0][0].global_step == dt.global_step
+
+
+# ---- H: the one dispatch against the per-name wrappers -----------------------------------------------------------------
+DISPATCH_NAMES = ["Adagrad", "SGD", "RMSprop", "Adamax", "Adam", "Adadelta", "Ftrl", "Nadam", "LazyAdam", "RowWiseAdagrad"]
+
+
+def _quarter_on_id_0(seed, B, V):
+    """A batch whose id 0 holds a quarter of the pairs on both sides (every fourth row, every fourth col) and ten more."""
+    row, col, w, y = make_batch(seed, B, V, zipf=False)
+    row, col = 1 + row % (V - 1), 1 + col % (V - 1)
+    clash = row == col
+    col[clash] = col[clash] % (V - 1) + 1
+    row[0::4], row[2:40:4] = 0, 0
+    col[1::4], col[3:40:4] = 0, 0
+    return row, col, w, y
+
+
+@gpu
+@pytest.mark.parametrize("optimizer", DISPATCH_NAMES)
+def test_h_step_dispatch_equals_the_names_own_wrapper(hip, optimizer):
+    """GloveHip.step picks the entry point from tables.optimizer; step_adagrad / step_adam / step_sparse are the wrappers it
+    stands for.  Three steps through each from the same seed, d = 50 on a stride of 52 (padding columns), chunks of 8 with an id
+    of more than 8 chunks on both sides (the workgroup path): both reach the same launches, so all four variables, every
+    slot, scalars, global_step and the loss are bitwise equal.  No tolerance."""
+    from trainer.hip_api import DeviceTables, make_hyper
+    V, d, B, cap = 97, 50, 256, 8
+    batches = [_quarter_on_id_0(900 + s, B, V) for s in range(3)]
+    for row, col, _, _ in batches:
+        assert int((row == 0).sum()) == int((col == 0).sum()) == B // 4 + 10 > 8 * cap and not (row == col).any()     # id 0: more than HEAVY_CHUNKS chunks
+    plans = [hip.build_plan(*to_dev(*b), V, chunk_cap=cap) for b in batches]
+    h = make_hyper(learning_rate=0.01, batch_size=B, optimizer=optimizer)
+    runs = []
+    for arm in ("dispatch", "wrapper"):
+        dt = DeviceTables(V, d, optimizer, seed=3)
+        assert dt.d == 52
+        G = hip.dense_grad_buffer(dt) if optimizer in ("Adam", "RMSprop", "Nadam") else None
+        loss_out = torch.zeros(4, device="cuda:0")
+        for plan in plans:
+            if arm == "dispatch":
+                hip.step(plan, dt, h, G, loss_out)
+            elif optimizer == "Adagrad":
+                hip.step_adagrad(plan, dt, h, loss_out)
+            elif optimizer == "Adam":
+                hip.step_adam(plan, dt, h, G, loss_out)
+            else:
+                hip.step_sparse(plan, dt, h, G, loss_out)
+        _assert_buffer_zero(G)
+        runs.append((dt, loss_out))
+    (a, la), (b, lb) = runs
+    assert a.global_step == b.global_step == 3
+    for n in ("R", "C", "br", "bc"):
+        assert torch.equal(getattr(a, n), getattr(b, n)), n
+        assert torch.equal(a.s1[n], b.s1[n]), "slot1 " + n
+        assert set(a.s2) == set(b.s2)
+        if n in a.s2:
+            assert torch.equal(a.s2[n], b.s2[n]), "slot2 " + n
+    assert torch.equal(a.scalars, b.scalars) and torch.equal(la, lb)
+    assert float(a.R.abs().max()) > 0 and not torch.equal(a.R, DeviceTables(V, d, optimizer, seed=3).R)       # the steps moved something
