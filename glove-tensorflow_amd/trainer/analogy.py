@@ -1,10 +1,11 @@
 """`python -m trainer.analogy --job-dir J --questions FILE [--embeddings row|col|sum] [--top-k 1] [--batch-size 1024]
-[--restrict-vocab N] [--no-lowercase]`
+[--restrict-vocab N] [--no-lowercase] [--method 3cosadd|3cosmul] [--epsilon 0.001]`
 
 Scores the word-analogy questions `a : b :: c : ?` of a `questions-words.txt`-style file (`: section` lines, then lines of
 four tokens) against the newest checkpoint of J: 3CosAdd on the GPU (include/glove_eval_hip.h), the stock intrinsic check
 of GloVe and word2vec embeddings, which the reference does not have.  Writes J/eval/analogy.json.  One process: checkpoints
-hold the whole model in vocabulary order however the run was sharded or relabelled.
+hold the whole model in vocabulary order however the run was sharded or relabelled.  `--method 3cosmul` scores by Levy &
+Goldberg's 3CosMul instead (include/glove_eval_sim_hip.h) and writes J/eval/analogy_3cosmul.json.
 
 This module holds the file format and the bookkeeping; `Estimator.evaluate_analogies` does the work.
 """
@@ -20,6 +21,7 @@ from trainer import config
 logger = logging.getLogger(__name__)
 SKIPPED_TOKEN = "<UNK>"
 EMBEDDINGS = ("row", "col", "sum")
+METHODS = ("3cosadd", "3cosmul")
 SYNTACTIC_PREFIX = "gram"       # word2vec's convention: sections named gram1-adjective-to-adverb, ... are syntactic
 
 
@@ -87,11 +89,12 @@ def summarize(sections, counts, hits) -> dict:
 
 
 def main(job_dir=config.JOB_DIR, questions=None, embeddings="row", top_k=1, batch_size=1024, restrict_vocab=None,
-         no_lowercase=False, **_):
+         no_lowercase=False, method="3cosadd", epsilon=1e-3, **_):
     from trainer.estimator import Estimator
     params = json.loads(Path(job_dir, "params.json").read_text())
     return Estimator(params).evaluate_analogies(questions, embeddings=embeddings, top_k=top_k, batch_size=batch_size,
-                                                restrict_vocab=restrict_vocab, lowercase=not no_lowercase)
+                                                restrict_vocab=restrict_vocab, lowercase=not no_lowercase, method=method,
+                                                epsilon=epsilon)
 
 
 if __name__ == "__main__":
@@ -104,6 +107,8 @@ if __name__ == "__main__":
     cli.add_argument("--batch-size", type=int, default=1024, help="questions per GPU call (their scores are a [batch, V] matrix)")
     cli.add_argument("--restrict-vocab", type=int, default=None, help="use the first N vocabulary rows only, as table and as candidates")
     cli.add_argument("--no-lowercase", action="store_true", help="take the question words as written instead of lowercasing them")
+    cli.add_argument("--method", choices=METHODS, default="3cosadd", help="3cosadd: cos(b - a + c, v); 3cosmul: cos(b, v) cos(c, v) / (cos(a, v) + epsilon) on cosines shifted to [0, 1]")
+    cli.add_argument("--epsilon", type=float, default=0.001, help="3cosmul's guard against a zero denominator, in (0, 1]: the paper's value (gensim uses 1e-6)")
     try:
         main(**vars(cli.parse_args()))
     except KeyboardInterrupt:

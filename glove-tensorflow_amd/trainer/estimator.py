@@ -422,16 +422,10 @@ class Estimator:
         return rec
 
     # ---- word analogies (this build only: the reference has no intrinsic measure of the embeddings)
-    def evaluate_analogies(self, questions, embeddings="row", top_k=1, batch_size=1024, restrict_vocab=None,
-                           lowercase=True) -> dict:
-        """Scores the analogy questions `a : b :: c : ?` of the file `questions` (trainer.analogy: the format and the
-        counts) by 3CosAdd on the GPU (include/glove_eval_hip.h) and writes job_dir/eval/analogy.json.  `embeddings`:
-        the row table, the col table or their sum, the GloVe paper's W + W~; `restrict_vocab` N: the first N rows are
-        the table and the candidates.  One process, on the whole model."""
+    def _evaluation_table(self, embeddings, restrict_vocab):
+        """The table the intrinsic evaluations score: the row table, the col table or their sum (the GloVe paper's
+        W + W~), cut to its first `restrict_vocab` rows."""
         from trainer import analogy
-        from trainer.data_utils import read_vocab
-        if self.world > 1:
-            raise ValueError("evaluate_analogies runs in one process: checkpoints hold the whole model")
         if embeddings not in analogy.EMBEDDINGS:
             raise ValueError("--embeddings must be one of %s, got %r" % (", ".join(analogy.EMBEDDINGS), embeddings))
         tables = self.model.tables
@@ -440,7 +434,25 @@ class Estimator:
             if not 0 < restrict_vocab <= self.vocab_size:
                 raise ValueError("--restrict-vocab must lie in [1, %d], got %r" % (self.vocab_size, restrict_vocab))
             W = W[:restrict_vocab]
-        W = W.contiguous()
+        return W.contiguous()
+
+    def evaluate_analogies(self, questions, embeddings="row", top_k=1, batch_size=1024, restrict_vocab=None,
+                           lowercase=True, method="3cosadd", epsilon=1e-3) -> dict:
+        """Scores the analogy questions `a : b :: c : ?` of the file `questions` (trainer.analogy: the format and the
+        counts) on the GPU and writes job_dir/eval/analogy.json.  `method`: 3cosadd (include/glove_eval_hip.h) or
+        3cosmul with `epsilon` (include/glove_eval_sim_hip.h), whose record also names the method and epsilon and goes
+        to eval/analogy_3cosmul.json.  `embeddings`: the row table, the col table or their sum, the GloVe paper's
+        W + W~; `restrict_vocab` N: the first N rows are the table and the candidates.  One process, on the whole model."""
+        from trainer import analogy
+        from trainer.data_utils import read_vocab
+        if self.world > 1:
+            raise ValueError("evaluate_analogies runs in one process: checkpoints hold the whole model")
+        if method not in analogy.METHODS:
+            raise ValueError("--method must be one of %s, got %r" % (", ".join(analogy.METHODS), method))
+        if method == "3cosmul" and not 0.0 < epsilon <= 1.0:          # (NaN fails both comparisons)
+            raise ValueError("--epsilon must lie in (0, 1], got %r" % (epsilon,))
+        W = self._evaluation_table(embeddings, restrict_vocab)
+        tables = self.model.tables
         if not 1 <= top_k <= min(W.shape[0] - 3, 1024):
             raise ValueError("--top-k must lie in [1, min(rows - 3, 1024)] (a question's own three words are no candidates): "
                              "%d rows, got %r" % (W.shape[0], top_k))
@@ -448,17 +460,52 @@ class Estimator:
         kept, counts = analogy.lookup_questions(sections, read_vocab(self.params["vocab_txt"]), limit=restrict_vocab)
         if kept:
             abc = torch.tensor([q[:3] for q in kept], dtype=torch.int32).to(self.device)
-            _, idx = self.backend.analogy_topk(W, abc, top_k, batch_size)
+            if method == "3cosmul":
+                _, idx = self.backend.analogy_cosmul_topk(W, abc, top_k, epsilon, batch_size)
+            else:
+                _, idx = self.backend.analogy_topk(W, abc, top_k, batch_size)
             expected = torch.tensor([q[3] for q in kept], dtype=torch.int32)
             hits = (idx.cpu() == expected[:, None]).any(dim=1).tolist()
         else:
             hits = []
         rec = {"global_step": tables.global_step, "embeddings": embeddings, "top_k": top_k}
+        if method == "3cosmul":
+            rec.update(method=method, epsilon=epsilon)
         rec.update(analogy.summarize(sections, counts, hits))
         for s in rec["sections"] + [dict(rec["total"], name="total")]:
             logger.info("analogies, %s: %d of %d correct%s, %d skipped", s["name"] or "(unnamed)", s["correct"], s["total"],
                         "" if s["accuracy"] is None else " (%.2f %%)" % (100 * s["accuracy"]), s["skipped"])
-        path = os.path.join(self.params["job_dir"], "eval", "analogy.json")
+        path = os.path.join(self.params["job_dir"], "eval", "analogy_3cosmul.json" if method == "3cosmul" else "analogy.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(rec, f, indent=2)
+        return rec
+
+    # ---- word similarity (this build only, like the analogies)
+    def evaluate_word_pairs(self, pairs_file, embeddings="row", restrict_vocab=None, lowercase=True, delimiter=None,
+                            score_column=3) -> dict:
+        """Scores the word pairs of the file `pairs_file` (trainer.wordsim: the format and the statistics): the cosine of
+        every pair on the GPU (include/glove_eval_sim_hip.h) against the file's human scores, Spearman and Pearson, and
+        writes job_dir/eval/wordsim.json.  `embeddings` and `restrict_vocab` as in evaluate_analogies.  One process."""
+        from trainer import wordsim
+        from trainer.data_utils import read_vocab
+        if self.world > 1:
+            raise ValueError("evaluate_word_pairs runs in one process: checkpoints hold the whole model")
+        W = self._evaluation_table(embeddings, restrict_vocab)
+        rows = wordsim.parse_pairs(pairs_file, lowercase=lowercase, delimiter=delimiter, score_column=score_column)
+        ids, human, skipped = wordsim.lookup_pairs(rows, read_vocab(self.params["vocab_txt"]), limit=restrict_vocab)
+        if ids:
+            pairs = torch.tensor(ids, dtype=torch.int32).to(self.device)
+            cosines = self.backend.pair_cosine(W, pairs).cpu().tolist()
+        else:
+            cosines = []
+        rec = {"global_step": self.model.tables.global_step, "embeddings": embeddings,
+               "pairs_file": os.path.basename(str(pairs_file)), "pairs_total": len(rows), "pairs_seen": len(ids),
+               "skipped": skipped, "spearman": wordsim.spearman(cosines, human), "pearson": wordsim.pearson(cosines, human)}
+        logger.info("word similarity, %s: spearman %s, pearson %s on %d of %d pairs, %d skipped", rec["pairs_file"],
+                    *("n/a" if rec[key] is None else "%.4f" % rec[key] for key in ("spearman", "pearson")),
+                    rec["pairs_seen"], rec["pairs_total"], skipped)
+        path = os.path.join(self.params["job_dir"], "eval", "wordsim.json")
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as f:
             json.dump(rec, f, indent=2)

@@ -1,4 +1,5 @@
-"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h) and of libglove_eval_hip.so (include/glove_eval_hip.h).
+"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h) and of libglove_eval_hip.so (include/glove_eval_hip.h,
+include/glove_eval_sim_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -23,6 +24,7 @@ EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_ev
 
 GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
+GLOVE_EVAL_SIM_ABI_VERSION = 1      # include/glove_eval_sim_hip.h: the same library's second header, versioned on its own
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
 ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
@@ -65,6 +67,9 @@ EXPORTED_SYMBOLS = (
 
 # every symbol include/glove_eval_hip.h declares
 EVAL_EXPORTED_SYMBOLS = ("glove_eval_abi_version", "glove_analogy_workspace_bytes", "glove_analogy_topk_f32")
+# every symbol include/glove_eval_sim_hip.h declares (the same library)
+EVAL_SIM_EXPORTED_SYMBOLS = ("glove_eval_sim_abi_version", "glove_cosmul_workspace_bytes", "glove_cosmul_topk_f32",
+                             "glove_pair_cosine_f32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -194,7 +199,7 @@ _eval_lib = None
 
 
 def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h) and declare the prototypes, at the first call that needs it:
+    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h, include/glove_eval_sim_hip.h) and declare the prototypes, at the first call that needs it:
     training never loads it.  Raises if it is not built, like load_library."""
     global _eval_lib
     if _eval_lib is not None and path is None:
@@ -204,10 +209,17 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_eval_abi_version": (C.c_int, []),
         "glove_analogy_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "glove_analogy_topk_f32": (C.c_int, [vp, i32, i32, vp, i32, i32, vp, vp, vp, sz, vp]),
+        "glove_eval_sim_abi_version": (C.c_int, []),
+        "glove_cosmul_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "glove_cosmul_topk_f32": (C.c_int, [vp, i32, i32, vp, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
+        "glove_pair_cosine_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, vp]),
     }
     lib = _open(Path(path) if path else EVAL_LIB_PATH, protos)
     if lib.glove_eval_abi_version() != GLOVE_EVAL_ABI_VERSION:
         raise GloveHipError("ABI mismatch: eval library %d, binding %d" % (lib.glove_eval_abi_version(), GLOVE_EVAL_ABI_VERSION))
+    if lib.glove_eval_sim_abi_version() != GLOVE_EVAL_SIM_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: eval library (similarity entry points) %d, binding %d"
+                            % (lib.glove_eval_sim_abi_version(), GLOVE_EVAL_SIM_ABI_VERSION))
     if path is None:
         _eval_lib = lib
     return lib
@@ -1212,6 +1224,41 @@ class GloveHip:
             _check(lib.glove_analogy_topk_f32(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, _ptr(sims[s:s + m]), _ptr(idx[s:s + m]),
                                               _ptr(ws), ws.numel(), _stream()), "glove_analogy_topk_f32")
         return sims, idx
+
+    def analogy_cosmul_topk(self, W: torch.Tensor, abc: torch.Tensor, k: int, eps: float = 1e-3, batch: int = 1024):
+        """3CosMul word analogies (include/glove_eval_sim_hip.h): for the questions abc [n,3] = (a, b, c) the k rows v of
+        W [V,d] with the largest s(b, v) s(c, v) / (s(a, v) + eps), s = (1 + cos) / 2, a, b and c themselves left out ->
+        (scores, idx) [n,k], descending, ties to the lower id.  Walks the questions in batches through one workspace like
+        analogy_topk; a question's scores do not depend on its batch.  The ids of abc must lie in [0, V)."""
+        _require(W, torch.float32); _require(abc, torch.int32)
+        if W.dim() != 2 or abc.dim() != 2 or abc.shape[1] != 3:
+            raise GloveHipError("expected W [V,d] and abc [n,3]")
+        if batch < 1:
+            raise GloveHipError("batch must be positive, got %d" % batch)
+        lib = load_eval_library()
+        V, d = W.shape
+        n = int(abc.shape[0])
+        sims = torch.empty(n, k, dtype=torch.float32, device=W.device)
+        idx = torch.empty(n, k, dtype=torch.int32, device=W.device)
+        ws = torch.empty(max(lib.glove_cosmul_workspace_bytes(min(batch, n), V, d, k), 256), dtype=torch.uint8, device=W.device)
+        for s in range(0, max(n, 1), batch):      # (n == 0: one call, which checks the sizes and launches nothing)
+            m = min(batch, n - s)
+            _check(lib.glove_cosmul_topk_f32(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, float(eps), _ptr(sims[s:s + m]),
+                                             _ptr(idx[s:s + m]), _ptr(ws), ws.numel(), _stream()), "glove_cosmul_topk_f32")
+        return sims, idx
+
+    def pair_cosine(self, W: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
+        """The cosine of the rows pairs[i,0] and pairs[i,1] of W [V,d] -> [n] (include/glove_eval_sim_hip.h), the norms
+        clamped as in the PREDICT path.  The ids must lie in [0, V)."""
+        _require(W, torch.float32); _require(pairs, torch.int32)
+        if W.dim() != 2 or pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise GloveHipError("expected W [V,d] and pairs [n,2]")
+        lib = load_eval_library()
+        V, d = W.shape
+        n = int(pairs.shape[0])
+        out = torch.empty(n, dtype=torch.float32, device=W.device)
+        _check(lib.glove_pair_cosine_f32(_ptr(W), V, d, _ptr(pairs), n, _ptr(out), _stream()), "glove_pair_cosine_f32")
+        return out
 
     # ---- data prep
     def cooccurrence(self, tokens: torch.Tensor, V: int, context: int, cap: int | None = None):

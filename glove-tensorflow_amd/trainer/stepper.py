@@ -204,6 +204,12 @@ class HipBackend:
     def analogy_topk(self, W, abc, k, batch=1024):
         return self.hip.analogy_topk(W, abc, k, batch)
 
+    def analogy_cosmul_topk(self, W, abc, k, eps=1e-3, batch=1024):
+        return self.hip.analogy_cosmul_topk(W, abc, k, eps, batch)
+
+    def pair_cosine(self, W, pairs):
+        return self.hip.pair_cosine(W, pairs)
+
 
 def all_gather_rows(dist, recv, send, async_op=False):
     """recv[r] = rank r's `send` (equal shapes).  async_op: returns the work handle (wait() before reading recv)."""
