@@ -17,7 +17,10 @@ constexpr int kPartials = 4;       // per-block loss partials: sum w diff^2, sum
 
 // ---- diagnostic build only (-DGLOVE_STAMPS): per-wave wall-clock stamps (s_memrealtime, 100 MHz)
 #ifdef GLOVE_STAMPS
-extern __device__ unsigned long long *g_stamps;     // [waves][8], set by glove_debug_set_stamps
+// (no relocatable device code: every translation unit whose kernels stamp holds a copy of its own, set through the host function
+// that GLOVE_STAMPS_SETTER(name) defines there; glove_debug_set_stamps calls each of them)
+static __device__ unsigned long long *g_stamps = nullptr;     // [waves][8], set by glove_debug_set_stamps
+#define GLOVE_STAMPS_SETTER(name) int name(void *p) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &p, sizeof(p)); }
 __device__ inline void stamp(int slot)
 {
     if ((threadIdx.x & 63) == 0 && g_stamps)
@@ -250,9 +253,9 @@ inline int64_t most_chunks(const glove_plan *p, bool row)
 // (lanes per row, float4 per lane) covering d4 = d/4 float4 per embedding row with the least
 // idle lanes; a wave64 holds 64/LPR rows at a time.
 struct RowShape { int lpr, nv; };
-inline RowShape pick_row_shape(int d4)
+constexpr RowShape pick_row_shape(int d4)
 {
-    const RowShape cands[] = {{16, 1}, {32, 1}, {16, 2}, {64, 1}, {32, 2}, {32, 3}, {64, 2}, {64, 3}, {64, 4}};
+    const RowShape cands[] = {{16, 1}, {32, 1}, {64, 1}, {32, 3}, {64, 2}, {64, 3}, {64, 4}};
     RowShape best = {0, 0};
     int best_slots = 1 << 30;
     for (const RowShape &c : cands) {
@@ -264,27 +267,27 @@ inline RowShape pick_row_shape(int d4)
 
 // Shapes of the gather passes (rowpass / colpass): narrow groups (8 lanes = one 128-B line per
 // load at d = 64) put 8 chunks on a wave, which divides the per-pair bookkeeping instructions.
-inline RowShape pick_pass_shape(int d4)
+constexpr RowShape pick_pass_shape(int d4)
 {
     if (d4 <= 8) return RowShape{8, 1};
     if (d4 <= 16) return RowShape{8, 2};      // d = 64: measured faster than 16 x 1 (A/B, same process)
     return pick_row_shape(d4);                // wider rows: 16-lane x 5 measured slower than 32 x 3 at d = 300
 }
 
+// The shapes kernels are built for, written once: X(LPR, NV, ...) for every shape the rule selects for some d4 = 1 .. kMaxD4
+// (checked below, both ways).  A shape no width selects is a build of every shaped kernel that nothing can launch.
+#define GLOVE_PASS_SHAPES(X, ...) X(8, 1, __VA_ARGS__) X(8, 2, __VA_ARGS__) X(32, 1, __VA_ARGS__) X(32, 3, __VA_ARGS__) \
+    X(64, 1, __VA_ARGS__) X(64, 2, __VA_ARGS__) X(64, 3, __VA_ARGS__) X(64, 4, __VA_ARGS__)
+#define GLOVE_ROW_SHAPES(X, ...) X(16, 1, __VA_ARGS__) X(32, 1, __VA_ARGS__) X(32, 3, __VA_ARGS__) \
+    X(64, 1, __VA_ARGS__) X(64, 2, __VA_ARGS__) X(64, 3, __VA_ARGS__) X(64, 4, __VA_ARGS__)
+constexpr int kMaxD4 = 256;        // float4 per row of the widest shape (64 x 4)
+
+#define GLOVE_SHAPE_CASE_(LPR, NV, CALL) case LPR * 8 + NV: { CALL(LPR, NV); } break;
 #define GLOVE_DISPATCH_PASS_SHAPE(shape, CALL)                                  \
     do {                                                                        \
         const int key_ = (shape).lpr * 8 + (shape).nv;                          \
         switch (key_) {                                                         \
-        case 8 * 8 + 1: { CALL(8, 1); } break;                                  \
-        case 8 * 8 + 2: { CALL(8, 2); } break;                                  \
-        case 16 * 8 + 2: { CALL(16, 2); } break;                                \
-        case 32 * 8 + 1: { CALL(32, 1); } break;                                \
-        case 32 * 8 + 2: { CALL(32, 2); } break;                                \
-        case 32 * 8 + 3: { CALL(32, 3); } break;                                \
-        case 64 * 8 + 1: { CALL(64, 1); } break;                                \
-        case 64 * 8 + 2: { CALL(64, 2); } break;                                \
-        case 64 * 8 + 3: { CALL(64, 3); } break;                                \
-        case 64 * 8 + 4: { CALL(64, 4); } break;                                \
+        GLOVE_PASS_SHAPES(GLOVE_SHAPE_CASE_, CALL)                              \
         default: return GLOVE_E_BADARG;                                         \
         }                                                                       \
     } while (0)
@@ -293,17 +296,33 @@ inline RowShape pick_pass_shape(int d4)
     do {                                                                        \
         const int key_ = (shape).lpr * 8 + (shape).nv;                          \
         switch (key_) {                                                         \
-        case 16 * 8 + 1: { CALL(16, 1); } break;                                \
-        case 16 * 8 + 2: { CALL(16, 2); } break;                                \
-        case 32 * 8 + 1: { CALL(32, 1); } break;                                \
-        case 32 * 8 + 2: { CALL(32, 2); } break;                                \
-        case 32 * 8 + 3: { CALL(32, 3); } break;                                \
-        case 64 * 8 + 1: { CALL(64, 1); } break;                                \
-        case 64 * 8 + 2: { CALL(64, 2); } break;                                \
-        case 64 * 8 + 3: { CALL(64, 3); } break;                                \
-        case 64 * 8 + 4: { CALL(64, 4); } break;                                \
+        GLOVE_ROW_SHAPES(GLOVE_SHAPE_CASE_, CALL)                               \
         default: return GLOVE_E_BADARG;                                         \
         }                                                                       \
     } while (0)
+
+// ... and the check: every width up to kMaxD4 gets a listed shape (the `default` above is unreachable for supported widths), and
+// every listed shape is some width's
+#define GLOVE_SHAPE_IS_(LPR, NV, s) || ((s).lpr == LPR && (s).nv == NV)
+constexpr bool pass_shape_listed(RowShape s) { return false GLOVE_PASS_SHAPES(GLOVE_SHAPE_IS_, s); }
+constexpr bool row_shape_listed(RowShape s) { return false GLOVE_ROW_SHAPES(GLOVE_SHAPE_IS_, s); }
+template <RowShape (*PICK)(int)> constexpr bool shape_picked(int lpr, int nv)
+{
+    for (int d4 = 1; d4 <= kMaxD4; ++d4)
+        if (PICK(d4).lpr == lpr && PICK(d4).nv == nv) return true;
+    return false;
+}
+constexpr bool shape_lists_exact()
+{
+    for (int d4 = 1; d4 <= kMaxD4; ++d4)
+        if (!pass_shape_listed(pick_pass_shape(d4)) || !row_shape_listed(pick_row_shape(d4))) return false;
+#define GLOVE_SHAPE_PICKED_(LPR, NV, PICK) if (!shape_picked<PICK>(LPR, NV)) return false;
+    GLOVE_PASS_SHAPES(GLOVE_SHAPE_PICKED_, pick_pass_shape)
+    GLOVE_ROW_SHAPES(GLOVE_SHAPE_PICKED_, pick_row_shape)
+#undef GLOVE_SHAPE_PICKED_
+    return true;
+}
+static_assert(shape_lists_exact(), "GLOVE_PASS_SHAPES / GLOVE_ROW_SHAPES list exactly the shapes pick_pass_shape / pick_row_shape select");
+#undef GLOVE_SHAPE_IS_
 
 }  // namespace glove
