@@ -534,6 +534,9 @@ int glove_eval_logistic_f32(const int32_t *row, const int32_t *col, const float 
  * For n query ids: sims/idx [n,k] sorted descending (ties: lower id first) over all V ROW embeddings; d = row
  * stride in floats (multiple of 4), 1 <= k <= min(V, 1024).  The similarity matrix is the one GEMM of the path and
  * runs on the matrix cores in exact f32 (v_mfma_f32_32x32x2_f32); the top-k is a staged selection.
+ * Non-finite rows: a row of R that holds a NaN or an infinity scores NaN against every finite query (its inverse norm
+ * is 0 or its dot product NaN), NaN loses every comparison of the selection, and such a row is never returned as long
+ * as k is no larger than the number of finite rows: the result is that of the finite rows alone (tests/test_gpu_topk_order.py).
  * ws: glove_topk_workspace_bytes. */
 size_t glove_topk_workspace_bytes(int32_t n, int32_t V, int32_t k);
 int glove_topk_cosine_f32(const float *R, int32_t V, int32_t d, const int32_t *query_ids, int32_t n,

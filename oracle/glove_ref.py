@@ -582,7 +582,7 @@ def cooccurrence(token_ids, context_size):
     n = len(tok)
     V = int(tok.max()) + 1 if n else 0
     keys, vals = [], []
-    for k in range(1, context_size + 1):
+    for k in range(1, min(context_size, n - 1) + 1):     # (offsets of n and more pair nothing: tok[:n - k] would wrap)
         a, b = tok[:n - k], tok[k:]
         keep = a != b
         keys.append(a[keep] * V + b[keep])

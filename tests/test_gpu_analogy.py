@@ -1,8 +1,10 @@
 """Word-analogy top-k (3CosAdd) on the GPU: glove_analogy_topk_f32 of libglove_eval_hip.so against the float64 reference
 of tests/analogy_ref.py, and `python -m trainer.analogy` end to end.
 
-The shapes are the smallest that cross every boundary the kernels have: a query tile of 128, a vocabulary tile of 128, a
-k-slab of 32, a top-k segment of 4,096 candidates, and the row shapes of the lane-group kernels.
+The shapes are the smallest that cross the boundaries of the GEMM and the selection: a query tile of 128, a vocabulary
+tile of 128, a k-slab of 32 and a top-k segment of 4,096 candidates.  Of the seven row shapes of the lane-group kernels
+their widths (8 .. 300) reach three, 16 x 1, 32 x 1 and 32 x 3: tests/test_gpu_eval_row_shapes.py runs every shape at its
+first and its last width, tests/test_gpu_topk_order.py pins the selection's order on exact ties.
 
 Tolerances.  Scores: rtol 1e-5, atol 1e-6, the figures of test_topk_cosine (the same GEMM, one more rounding per query
 element); the same formula in float32 NumPy deviates from float64 by 2.8e-7 at most over the six parity cases (the kernel: 2.9e-7 on an MI355X).  Ids

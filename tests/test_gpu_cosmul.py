@@ -2,8 +2,9 @@
 tests/cosmul_ref.py, and `python -m trainer.analogy --method 3cosmul` end to end.
 
 The shapes and the question generator are those of tests/test_gpu_analogy.py: they cross a vocabulary tile of 128, a
-k-slab of 32 (d below it, and no multiple of it), a top-k segment of 4,096 candidates, the row shapes of the lane-group
-kernels, and question counts that are no multiple of 32, 64 or 128 (the question tile is 64).
+k-slab of 32 (d below it, and no multiple of it), a top-k segment of 4,096 candidates, and question counts that are no
+multiple of 32, 64 or 128 (the question tile is 64).  The row shapes of the lane-group kernels beyond the three these
+widths reach are run by tests/test_gpu_eval_row_shapes.py.
 
 Tolerances.  Scores: rtol 1e-5, atol 1e-6, the project's figures for this GEMM.  The same formula in float32 NumPy
 deviates from float64 by 8.3e-7 relative at most (4.8e-6 absolute, at scores up to 7.5) over the six parity cases with
