@@ -15,6 +15,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 from trainer.config_utils import check_shard_balance, parse_args
@@ -508,6 +509,80 @@ class Estimator:
         path = os.path.join(self.params["job_dir"], "eval", "wordsim.json")
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as f:
+            json.dump(rec, f, indent=2)
+        return rec
+
+    # ---- concept categorization and word classes (this build only): spherical k-means, include/glove_eval_cluster_hip.h
+    def evaluate_categorization(self, categories_file, embeddings="row", restrict_vocab=None, lowercase=True, delimiter=None,
+                                word_column=1, category_column=2, clusters=None, restarts=10, iterations=100, seed=0) -> dict:
+        """Clusters the words of the gold file `categories_file` (trainer.categorize: the format and the purity) by
+        spherical k-means on the GPU, `restarts` runs of at most `iterations` assign passes, and writes
+        job_dir/eval/categorization.json: the purity of the run with the best objective, and the purities' mean, minimum
+        and maximum over the runs.  `clusters` defaults to the gold categories among the words kept.  `embeddings` and
+        `restrict_vocab` as in evaluate_analogies.  One process."""
+        from trainer import categorize
+        from trainer.data_utils import read_vocab
+        if self.world > 1:
+            raise ValueError("evaluate_categorization runs in one process: checkpoints hold the whole model")
+        if restarts < 1 or iterations < 1:
+            raise ValueError("--restarts and --iterations must be positive, got %r and %r" % (restarts, iterations))
+        W = self._evaluation_table(embeddings, restrict_vocab)
+        rows = categorize.parse_categories(categories_file, lowercase=lowercase, delimiter=delimiter, word_column=word_column,
+                                           category_column=category_column)
+        ids, gold, skipped, duplicates = categorize.lookup_words(rows, read_vocab(self.params["vocab_txt"]), limit=restrict_vocab)
+        categories = len(set(gold))
+        K = categories if clusters is None else clusters
+        if not 1 <= K <= len(ids):
+            raise ValueError("--clusters must lie in [1, the %d words kept], got %r" % (len(ids), K))
+        res = self.backend.kmeans(W, torch.tensor(ids, dtype=torch.int32).to(self.device), K, seed=seed, restarts=restarts,
+                                  iterations=iterations)
+        assign = res.assign.cpu().tolist()
+        purities = [categorize.purity(a.cpu().tolist(), gold) for a in res.assignments]
+        rec = {"global_step": self.model.tables.global_step, "embeddings": embeddings,
+               "categories_file": os.path.basename(str(categories_file)), "words_total": len(rows), "words_seen": len(ids),
+               "skipped": skipped, "duplicates": duplicates, "categories": categories, "clusters": K, "restarts": restarts,
+               "seed": seed, "iterations": res.iterations, "converged": bool(res.converged), "objective": res.objective,
+               "purity": categorize.purity(assign, gold), "purity_mean": float(np.mean(purities)),
+               "purity_min": min(purities), "purity_max": max(purities),
+               "sizes": np.bincount(np.asarray(assign, np.int64), minlength=K).tolist()}
+        logger.info("categorization, %s: purity %.4f (mean %.4f over %d runs) on %d of %d words in %d clusters, %d skipped, "
+                    "%d duplicates", rec["categories_file"], rec["purity"], rec["purity_mean"], restarts, len(ids), len(rows), K,
+                    skipped, duplicates)
+        path = os.path.join(self.params["job_dir"], "eval", "categorization.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(rec, f, indent=2)
+        return rec
+
+    def word_classes(self, classes, embeddings="row", restrict_vocab=None, iterations=10, restarts=1, seed=0) -> dict:
+        """word2vec's -classes: spherical k-means of the vocabulary's rows ("<UNK>" left out) into `classes` clusters on
+        the GPU; writes job_dir/classes.txt, lines `token class` in vocabulary order, and job_dir/eval/classes.json.
+        `embeddings` and `restrict_vocab` as in evaluate_analogies.  One process."""
+        from trainer.analogy import SKIPPED_TOKEN
+        from trainer.data_utils import read_vocab
+        if self.world > 1:
+            raise ValueError("word_classes runs in one process: checkpoints hold the whole model")
+        if restarts < 1 or iterations < 1:
+            raise ValueError("--restarts and --iterations must be positive, got %r and %r" % (restarts, iterations))
+        W = self._evaluation_table(embeddings, restrict_vocab)
+        vocab = read_vocab(self.params["vocab_txt"])
+        ids = [i for i, token in enumerate(vocab[:W.shape[0]]) if token != SKIPPED_TOKEN]
+        if classes is None or not 1 <= classes <= len(ids):
+            raise ValueError("--classes must lie in [1, the %d words], got %r" % (len(ids), classes))
+        res = self.backend.kmeans(W, torch.tensor(ids, dtype=torch.int32).to(self.device), classes, seed=seed,
+                                  restarts=restarts, iterations=iterations)
+        assign = res.assign.cpu().tolist()
+        sizes = np.bincount(np.asarray(assign, np.int64), minlength=classes)
+        job_dir = self.params["job_dir"]
+        os.makedirs(os.path.join(job_dir, "eval"), exist_ok=True)
+        with open(os.path.join(job_dir, "classes.txt"), "w", encoding="utf8") as f:
+            f.writelines("%s %d\n" % (vocab[i], c) for i, c in zip(ids, assign))
+        rec = {"global_step": self.model.tables.global_step, "embeddings": embeddings, "words": len(ids), "classes": classes,
+               "iterations": res.iterations, "converged": bool(res.converged), "objective": res.objective,
+               "empty": int((sizes == 0).sum()), "largest": int(sizes.max()), "smallest": int(sizes.min())}
+        logger.info("word classes: %d words in %d classes after %d iterations (%s), sizes %d .. %d, %d empty", len(ids), classes,
+                    res.iterations, "converged" if res.converged else "not converged", rec["smallest"], rec["largest"], rec["empty"])
+        with open(os.path.join(job_dir, "eval", "classes.json"), "w") as f:
             json.dump(rec, f, indent=2)
         return rec
 

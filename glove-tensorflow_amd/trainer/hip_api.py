@@ -1,5 +1,5 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h) and of libglove_eval_hip.so (include/glove_eval_hip.h,
-include/glove_eval_sim_hip.h).
+include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -11,7 +11,9 @@ import ctypes as C
 import logging
 import os
 from pathlib import Path
+from typing import NamedTuple
 
+import numpy as np
 import torch
 
 from trainer.optimizers import BY_CODE, OPTIMIZERS, names
@@ -25,6 +27,7 @@ EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_ev
 GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
 GLOVE_EVAL_SIM_ABI_VERSION = 1      # include/glove_eval_sim_hip.h: the same library's second header, versioned on its own
+GLOVE_EVAL_CLUSTER_ABI_VERSION = 1  # include/glove_eval_cluster_hip.h: the third header (spherical k-means), likewise
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
 ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
@@ -70,6 +73,10 @@ EVAL_EXPORTED_SYMBOLS = ("glove_eval_abi_version", "glove_analogy_workspace_byte
 # every symbol include/glove_eval_sim_hip.h declares (the same library)
 EVAL_SIM_EXPORTED_SYMBOLS = ("glove_eval_sim_abi_version", "glove_cosmul_workspace_bytes", "glove_cosmul_topk_f32",
                              "glove_pair_cosine_f32")
+# every symbol include/glove_eval_cluster_hip.h declares (the same library)
+EVAL_CLUSTER_EXPORTED_SYMBOLS = ("glove_eval_cluster_abi_version", "glove_kmeans_workspace_bytes", "glove_kmeans_assign_f32",
+                                 "glove_kmeans_update_f32")
+KMEANS_MAX_CLUSTERS = 4096
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -199,7 +206,7 @@ _eval_lib = None
 
 
 def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h, include/glove_eval_sim_hip.h) and declare the prototypes, at the first call that needs it:
+    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h, include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and declare the prototypes, at the first call that needs it:
     training never loads it.  Raises if it is not built, like load_library."""
     global _eval_lib
     if _eval_lib is not None and path is None:
@@ -213,6 +220,10 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_cosmul_workspace_bytes": (sz, [i32, i32, i32, i32]),
         "glove_cosmul_topk_f32": (C.c_int, [vp, i32, i32, vp, i32, i32, C.c_float, vp, vp, vp, sz, vp]),
         "glove_pair_cosine_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, vp]),
+        "glove_eval_cluster_abi_version": (C.c_int, []),
+        "glove_kmeans_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "glove_kmeans_assign_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]),
+        "glove_kmeans_update_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
     }
     lib = _open(Path(path) if path else EVAL_LIB_PATH, protos)
     if lib.glove_eval_abi_version() != GLOVE_EVAL_ABI_VERSION:
@@ -220,6 +231,9 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_eval_sim_abi_version() != GLOVE_EVAL_SIM_ABI_VERSION:
         raise GloveHipError("ABI mismatch: eval library (similarity entry points) %d, binding %d"
                             % (lib.glove_eval_sim_abi_version(), GLOVE_EVAL_SIM_ABI_VERSION))
+    if lib.glove_eval_cluster_abi_version() != GLOVE_EVAL_CLUSTER_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: eval library (clustering entry points) %d, binding %d"
+                            % (lib.glove_eval_cluster_abi_version(), GLOVE_EVAL_CLUSTER_ABI_VERSION))
     if path is None:
         _eval_lib = lib
     return lib
@@ -857,6 +871,20 @@ def _same_optimizer(tables, hyper):
     return spec
 
 
+class KMeansResult(NamedTuple):
+    """What GloveHip.kmeans returns: the winning run's last assignment [n] int32, its cosines [n], the centroids [K,d]
+    that produced them, the assign passes it ran, whether two successive assignments agreed, its objective (the sum of
+    the cosines, float64 on the host), and of all restarts the objectives and the last assignments."""
+    assign: torch.Tensor
+    cos: torch.Tensor
+    centroids: torch.Tensor
+    iterations: int
+    converged: bool
+    objective: float
+    objectives: list
+    assignments: list
+
+
 class GloveHip:
     """Thin object wrapper over the C ABI; one instance per process/GPU."""
 
@@ -1259,6 +1287,98 @@ class GloveHip:
         out = torch.empty(n, dtype=torch.float32, device=W.device)
         _check(lib.glove_pair_cosine_f32(_ptr(W), V, d, _ptr(pairs), n, _ptr(out), _stream()), "glove_pair_cosine_f32")
         return out
+
+    # ---- spherical k-means (include/glove_eval_cluster_hip.h)
+    def _kmeans_args(self, W, ids, centroids, assign=None):
+        _require(W, torch.float32); _require(ids, torch.int32); _require(centroids, torch.float32)
+        if W.dim() != 2 or ids.dim() != 1 or centroids.dim() != 2 or centroids.shape[1] != W.shape[1]:
+            raise GloveHipError("expected W [V,d], ids [n] and centroids [K,d] of W's row stride")
+        if assign is not None:
+            _require(assign, torch.int32, int(ids.numel()))
+            if assign.dim() != 1:
+                raise GloveHipError("expected assign [n]")
+        return int(W.shape[0]), int(W.shape[1]), int(ids.numel()), int(centroids.shape[0])
+
+    def kmeans_workspace(self, n: int, V: int, d: int, K: int, device) -> torch.Tensor:
+        """The one workspace of kmeans_assign and kmeans_update for these sizes."""
+        need = load_eval_library().glove_kmeans_workspace_bytes(n, V, d, K)
+        if need == 0:
+            raise GloveHipError("k-means takes d %% 4 == 0 up to 1024, 0 <= n <= 65535 * 128 and 1 <= K <= %d: got n = %d, "
+                                "V = %d, d = %d, K = %d" % (KMEANS_MAX_CLUSTERS, n, V, d, K))
+        return torch.empty(need, dtype=torch.uint8, device=device)
+
+    def kmeans_assign(self, W: torch.Tensor, ids: torch.Tensor, centroids: torch.Tensor, ws: torch.Tensor | None = None):
+        """The closest of the centroids [K,d] by cosine for every point W[ids[i]] -> (assign [n] int32, cos [n]): ties to
+        the lower centroid, a zero row to cluster 0 with cosine 0.  The ids must lie in [0, V): the kernels do not look."""
+        V, d, n, K = self._kmeans_args(W, ids, centroids)
+        lib = load_eval_library()
+        ws = self.kmeans_workspace(n, V, d, K, W.device) if ws is None else ws
+        assign = torch.empty(n, dtype=torch.int32, device=W.device)
+        cos = torch.empty(n, dtype=torch.float32, device=W.device)
+        _check(lib.glove_kmeans_assign_f32(_ptr(W), V, d, _ptr(ids), n, _ptr(centroids), K, _ptr(assign), _ptr(cos),
+                                           _ptr(ws), ws.numel(), _stream()), "glove_kmeans_assign_f32")
+        return assign, cos
+
+    def kmeans_update(self, W: torch.Tensor, ids: torch.Tensor, assign: torch.Tensor, centroids: torch.Tensor,
+                      ws: torch.Tensor | None = None):
+        """The unit-length sums of each cluster's unit rows -> (centroids [K,d], counts [K] int32); an empty cluster keeps
+        its row of `centroids`.  Bitwise repeatable (a fixed summation order, no float atomics)."""
+        V, d, n, K = self._kmeans_args(W, ids, centroids, assign)
+        lib = load_eval_library()
+        ws = self.kmeans_workspace(n, V, d, K, W.device) if ws is None else ws
+        if n == 0:                      # the library leaves its outputs untouched: every cluster is empty
+            return centroids.clone(), torch.zeros(K, dtype=torch.int32, device=W.device)
+        out = torch.empty_like(centroids)
+        counts = torch.empty(K, dtype=torch.int32, device=W.device)
+        _check(lib.glove_kmeans_update_f32(_ptr(W), V, d, _ptr(ids), n, _ptr(assign), _ptr(centroids), K, _ptr(out),
+                                           _ptr(counts), _ptr(ws), ws.numel(), _stream()), "glove_kmeans_update_f32")
+        return out, counts
+
+    def kmeans(self, W: torch.Tensor, ids: torch.Tensor, K: int, seed: int = 0, restarts: int = 1, iterations: int = 100,
+               init: torch.Tensor | None = None) -> KMeansResult:
+        """Spherical k-means of the points W[ids[i]] into K clusters (include/glove_eval_cluster_hip.h).  Run r of
+        `restarts` starts from the unit rows of the points sorted(numpy.random.default_rng([seed, r]).choice(n, K,
+        replace=False)); `init` [K,d] gives the one run's initial centroids instead.  A run assigns, stops when the
+        assignment repeats (converged) or after `iterations` assign passes, and otherwise updates; its result is the
+        last assignment with the centroids that produced it.  The run with the largest sum of cosines wins, ties to the
+        lower r.  One workspace serves every call; the host compares successive assignments."""
+        _require(W, torch.float32); _require(ids, torch.int32)
+        if W.dim() != 2 or ids.dim() != 1:
+            raise GloveHipError("expected W [V,d] and ids [n]")
+        n = int(ids.numel())
+        if iterations < 1 or restarts < 1:
+            raise GloveHipError("iterations and restarts must be positive, got %d and %d" % (iterations, restarts))
+        if init is not None:
+            if restarts != 1:
+                raise GloveHipError("explicit initial centroids make one run: restarts must be 1, got %d" % restarts)
+            if init.dim() != 2 or init.shape[0] != K:
+                raise GloveHipError("expected init [K,d]")
+        elif not 1 <= K <= n:
+            raise GloveHipError("K must lie in [1, n = %d] to draw the initial centroids from the points, got %d" % (n, K))
+        ws = self.kmeans_workspace(n, int(W.shape[0]), int(W.shape[1]), K, W.device)
+        best, objectives, assignments = None, [], []
+        for r in range(restarts):
+            if init is not None:
+                cents = init
+            else:
+                rows = np.sort(np.random.default_rng([seed, r]).choice(n, K, replace=False))
+                X = W[ids[torch.from_numpy(rows).to(ids.device)].long()]
+                cents = (X * torch.rsqrt(torch.clamp((X * X).sum(dim=1, keepdim=True), min=1e-12))).contiguous()
+            previous, converged, t = None, False, 0
+            while True:
+                t += 1
+                assign, cos = self.kmeans_assign(W, ids, cents, ws)
+                converged = previous is not None and torch.equal(assign, previous)
+                if converged or t == iterations:
+                    break
+                cents, _ = self.kmeans_update(W, ids, assign, cents, ws)
+                previous = assign
+            objective = float(cos.cpu().numpy().astype(np.float64).sum())
+            objectives.append(objective)
+            assignments.append(assign)
+            if best is None or objective > best.objective:
+                best = KMeansResult(assign, cos, cents, t, converged, objective, objectives, assignments)
+        return best
 
     # ---- data prep
     def cooccurrence(self, tokens: torch.Tensor, V: int, context: int, cap: int | None = None):

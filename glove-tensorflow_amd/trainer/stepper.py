@@ -210,6 +210,9 @@ class HipBackend:
     def pair_cosine(self, W, pairs):
         return self.hip.pair_cosine(W, pairs)
 
+    def kmeans(self, W, ids, K, seed=0, restarts=1, iterations=100, init=None):
+        return self.hip.kmeans(W, ids, K, seed=seed, restarts=restarts, iterations=iterations, init=init)
+
 
 def all_gather_rows(dist, recv, send, async_op=False):
     """recv[r] = rank r's `send` (equal shapes).  async_op: returns the work handle (wait() before reading recv)."""
