@@ -1,5 +1,5 @@
-"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h) and of libglove_eval_hip.so (include/glove_eval_hip.h,
-include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h).
+"""ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
+include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and of libglove_prep_hip.so (include/glove_cooc_stream_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -24,10 +24,14 @@ PKG_DIR = Path(__file__).resolve().parent.parent
 LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
 EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_eval_hip.h: scoring finished embeddings, a library of its own
 
+PREP_LIB_PATH = PKG_DIR / "lib" / "libglove_prep_hip.so"      # include/glove_cooc_stream_hip.h: counting a corpus chunk by chunk, a library of its own
+
 GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
 GLOVE_EVAL_SIM_ABI_VERSION = 1      # include/glove_eval_sim_hip.h: the same library's second header, versioned on its own
 GLOVE_EVAL_CLUSTER_ABI_VERSION = 1  # include/glove_eval_cluster_hip.h: the third header (spherical k-means), likewise
+GLOVE_COOC_STREAM_ABI_VERSION = 1   # include/glove_cooc_stream_hip.h (libglove_prep_hip.so)
+COOC_MERGE_TILE = 2048              # GLOVE_COOC_MERGE_TILE: merged positions one workgroup of glove_cooc_merge_u64 owns
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
 ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
@@ -77,6 +81,10 @@ EVAL_SIM_EXPORTED_SYMBOLS = ("glove_eval_sim_abi_version", "glove_cosmul_workspa
 EVAL_CLUSTER_EXPORTED_SYMBOLS = ("glove_eval_cluster_abi_version", "glove_kmeans_workspace_bytes", "glove_kmeans_assign_f32",
                                  "glove_kmeans_update_f32")
 KMEANS_MAX_CLUSTERS = 4096
+# every symbol include/glove_cooc_stream_hip.h declares (libglove_prep_hip.so)
+PREP_EXPORTED_SYMBOLS = ("glove_cooc_stream_abi_version", "glove_cooc_chunk_workspace_bytes", "glove_cooc_chunk_keys_i32",
+                         "glove_cooc_merge_workspace_bytes", "glove_cooc_merge_u64", "glove_cooc_finalize_workspace_bytes",
+                         "glove_cooc_finalize")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -236,6 +244,34 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
                             % (lib.glove_eval_cluster_abi_version(), GLOVE_EVAL_CLUSTER_ABI_VERSION))
     if path is None:
         _eval_lib = lib
+    return lib
+
+
+_prep_lib = None
+
+
+def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
+    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h) and declare the prototypes, at the first call that needs
+    it: training never loads it.  Raises if it is not built, like load_library."""
+    global _prep_lib
+    if _prep_lib is not None and path is None:
+        return _prep_lib
+    sz, i32, i64, vp = C.c_size_t, C.c_int32, C.c_int64, C.c_void_p
+    protos = {
+        "glove_cooc_stream_abi_version": (C.c_int, []),
+        "glove_cooc_chunk_workspace_bytes": (sz, [i64, i32]),
+        "glove_cooc_chunk_keys_i32": (C.c_int, [vp, i64, i64, i32, i32, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_cooc_merge_workspace_bytes": (sz, [i64, i64]),
+        "glove_cooc_merge_u64": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_cooc_finalize_workspace_bytes": (sz, [i64]),
+        "glove_cooc_finalize": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+    }
+    lib = _open(Path(path) if path else PREP_LIB_PATH, protos)
+    if lib.glove_cooc_stream_abi_version() != GLOVE_COOC_STREAM_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: prep library %d, binding %d"
+                            % (lib.glove_cooc_stream_abi_version(), GLOVE_COOC_STREAM_ABI_VERSION))
+    if path is None:
+        _prep_lib = lib
     return lib
 
 
@@ -1398,6 +1434,96 @@ class GloveHip:
                                                _ptr(nnz), cap, _ptr(ws), ws.numel(), _stream()),
                "glove_cooccurrence_i32")
         m = int(nnz.item())
+        if m > cap:
+            raise GloveHipError("co-occurrence table has %d entries, capacity %d" % (m, cap))
+        return row[:m], col[:m], cnt[:m], val[:m]
+
+    # ---- data prep, chunk by chunk (include/glove_cooc_stream_hip.h): what trainer.cooccur.CoocAccumulator drives
+    def _bytes(self, n: int, what: str) -> torch.Tensor:
+        if n == 0:
+            raise GloveHipError("%s: sizes out of range" % what)
+        return torch.empty(n, dtype=torch.uint8, device=self.device)
+
+    def cooc_chunk_keys_enqueue(self, tokens, n_own: int, V: int, context: int, keys_out, counts_out, n_out, ws=None):
+        """glove_cooc_chunk_keys_i32 on the current stream, nothing read back: tokens [n_total] int32 (own positions, then
+        the halo), keys_out / counts_out int64 [cap] (a key's bits are those of the header's uint64), n_out int64 [>= 2]."""
+        lib = load_prep_library()
+        _require(tokens, torch.int32); _require(keys_out, torch.int64); _require(n_out, torch.int64)
+        _require(counts_out, torch.int64, int(keys_out.numel()))
+        n_total = int(tokens.numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_cooc_chunk_workspace_bytes(n_total, context), "glove_cooc_chunk_workspace_bytes")
+        _check(lib.glove_cooc_chunk_keys_i32(_ptr(tokens), int(n_own), n_total, V, context, _ptr(keys_out), _ptr(counts_out),
+                                             _ptr(n_out), int(keys_out.numel()), _ptr(ws), ws.numel(), _stream()),
+               "glove_cooc_chunk_keys_i32")
+
+    def cooc_merge_enqueue(self, keys_a, counts_a, n_a, keys_b, counts_b, n_b, keys_out, counts_out, n_out, ws=None):
+        """glove_cooc_merge_u64 on the current stream, nothing read back; n_a, n_b, n_out are int64 device tensors."""
+        lib = load_prep_library()
+        for k, c in ((keys_a, counts_a), (keys_b, counts_b), (keys_out, counts_out)):
+            _require(k, torch.int64); _require(c, torch.int64, int(k.numel()))
+        for t in (n_a, n_b, n_out):
+            _require(t, torch.int64)
+        cap_a, cap_b = int(keys_a.numel()), int(keys_b.numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_cooc_merge_workspace_bytes(cap_a, cap_b), "glove_cooc_merge_workspace_bytes")
+        _check(lib.glove_cooc_merge_u64(_ptr(keys_a), _ptr(counts_a), _ptr(n_a), cap_a, _ptr(keys_b), _ptr(counts_b), _ptr(n_b),
+                                        cap_b, _ptr(keys_out), _ptr(counts_out), _ptr(n_out), int(keys_out.numel()),
+                                        _ptr(ws), ws.numel(), _stream()), "glove_cooc_merge_u64")
+
+    def cooc_finalize_enqueue(self, keys, counts, n, V: int, context: int, min_count: int, row, col, cnt, val, nnz, ws=None):
+        """glove_cooc_finalize on the current stream, nothing read back; n and nnz are int64 device tensors (nnz [>= 2])."""
+        lib = load_prep_library()
+        _require(keys, torch.int64); _require(counts, torch.int64, int(keys.numel())); _require(n, torch.int64)
+        cap = int(row.numel())
+        _require(row, torch.int32); _require(col, torch.int32, cap); _require(cnt, torch.int64, cap)
+        _require(val, torch.float64, cap); _require(nnz, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_cooc_finalize_workspace_bytes(int(keys.numel())), "glove_cooc_finalize_workspace_bytes")
+        _check(lib.glove_cooc_finalize(_ptr(keys), _ptr(counts), _ptr(n), int(keys.numel()), V, context, int(min_count),
+                                       _ptr(row), _ptr(col), _ptr(cnt), _ptr(val), _ptr(nnz), cap, _ptr(ws), ws.numel(),
+                                       _stream()), "glove_cooc_finalize")
+
+    def cooc_chunk_keys(self, tokens: torch.Tensor, n_own: int, V: int, context: int, cap: int | None = None):
+        """(keys int64, counts int64): the distinct (row, col, distance) keys of a chunk, ascending, and how often each
+        occurred.  tokens [n_own + halo]: a pair belongs to the chunk that owns its left position (one host sync for the size)."""
+        cap = int(cap if cap is not None else max(1, 2 * context * int(n_own)))
+        keys = torch.empty(cap, dtype=torch.int64, device=tokens.device)
+        counts = torch.empty(cap, dtype=torch.int64, device=tokens.device)
+        n_out = torch.zeros(2, dtype=torch.int64, device=tokens.device)
+        self.cooc_chunk_keys_enqueue(tokens, n_own, V, context, keys, counts, n_out)
+        m = int(n_out[0].item())
+        if m > cap:
+            raise GloveHipError("the chunk has %d distinct keys, capacity %d" % (m, cap))
+        return keys[:m], counts[:m]
+
+    def cooc_merge(self, keys_a, counts_a, keys_b, counts_b, keys_out=None, counts_out=None):
+        """The ascending union of two strictly ascending key tables, counts of shared keys summed -> (keys, counts), views
+        of `keys_out` / `counts_out` (default: fresh ones that hold both inputs).  One host sync for the size."""
+        n_a, n_b = int(keys_a.numel()), int(keys_b.numel())
+        if keys_out is None:
+            keys_out = torch.empty(max(1, n_a + n_b), dtype=torch.int64, device=keys_a.device)
+            counts_out = torch.empty_like(keys_out)
+        sizes = torch.tensor([n_a, n_b, 0, 0], dtype=torch.int64).to(keys_a.device)
+        self.cooc_merge_enqueue(keys_a, counts_a, sizes[0:1], keys_b, counts_b, sizes[1:2], keys_out, counts_out, sizes[2:4])
+        m = int(sizes[2].item())
+        if m > keys_out.numel():
+            raise GloveHipError("the merged table has %d keys, capacity %d" % (m, keys_out.numel()))
+        return keys_out[:m], counts_out[:m]
+
+    def cooc_finalize(self, keys, counts, V: int, context: int, min_count: int = 0, cap: int | None = None):
+        """(row i32, col i32, count i64, value f64) sorted by (row, col) from a key table: what `cooccurrence` returns for
+        the corpus the keys were counted from, bit for bit, cut to the pairs with count >= min_count (one host sync)."""
+        n = int(keys.numel())
+        cap = int(cap if cap is not None else max(1, n))
+        dev = keys.device
+        row = torch.empty(cap, dtype=torch.int32, device=dev)
+        col = torch.empty(cap, dtype=torch.int32, device=dev)
+        cnt = torch.empty(cap, dtype=torch.int64, device=dev)
+        val = torch.empty(cap, dtype=torch.float64, device=dev)
+        sizes = torch.tensor([n, 0, 0], dtype=torch.int64).to(dev)
+        self.cooc_finalize_enqueue(keys, counts, sizes[0:1], V, context, min_count, row, col, cnt, val, sizes[1:3])
+        m = int(sizes[1].item())
         if m > cap:
             raise GloveHipError("co-occurrence table has %d entries, capacity %d" % (m, cap))
         return row[:m], col[:m], cnt[:m], val[:m]

@@ -43,7 +43,12 @@ def create_vocabulary(text_tokens, vocab_size=VOCAB_SIZE, coverage=COVERAGE):
     """Tokens whose count reaches the count at which the cumulative token mass hits `coverage`
     (at most `vocab_size` of them), plus "<UNK>" carrying the rest; sorted by count, descending
     (reference text8.py:61-81).  Returns (tokens, counts, proportions) as lists/arrays in id order."""
-    counter = Counter(text_tokens)
+    return vocabulary_from_counts(Counter(text_tokens), vocab_size, coverage)
+
+
+def vocabulary_from_counts(counter: Counter, vocab_size=VOCAB_SIZE, coverage=COVERAGE):
+    """create_vocabulary from the token counts (first occurrences in corpus order): what trainer.cooccur feeds from a
+    Counter kept while the corpus streams by."""
     by_count = np.sort(np.fromiter(counter.values(), dtype=np.int64))[::-1]
     total = int(by_count.sum())
     cutoff = by_count[np.searchsorted(np.cumsum(by_count) / total, coverage)]
@@ -67,17 +72,35 @@ def glove_weight(values, alpha=0.75, x_max=100):
     return np.clip(np.power(np.asarray(values, dtype=np.float64) / x_max, alpha), 0, 1)
 
 
-def create_interaction_table(ids: np.ndarray, vocab, context_size=CONTEXT_SIZE, hip=None, device="cuda:0", seed=0):
+def create_interaction_table(ids: np.ndarray, vocab, context_size=CONTEXT_SIZE, hip=None, device="cuda:0", seed=0,
+                             chunk_tokens=None):
     """Symmetrised window co-occurrence table with the vocabulary columns joined in
-    (text8.py:84-126), rows in a seeded random order.  Returns a dict of numpy columns."""
+    (text8.py:84-126), rows in a seeded random order.  Returns a dict of numpy columns.
+    `chunk_tokens`: count the corpus in chunks of that many positions (trainer.cooccur.CoocAccumulator) instead of in one
+    call — the same table bit for bit, in bounded device memory."""
     import torch
     if hip is None:
         from trainer.hip_api import GloveHip
         hip = GloveHip(device)
-    tokens, counts, proportions = vocab
-    row, col, cnt, val = hip.cooccurrence(torch.from_numpy(ids).to(hip.device), len(tokens), context_size)
+    tokens = vocab[0]
+    if chunk_tokens:
+        from trainer.cooccur import CoocAccumulator, iter_chunks
+        acc = CoocAccumulator(len(tokens), context_size, hip)
+        for piece, n_own in iter_chunks([ids], chunk_tokens, context_size):
+            acc.add(piece, n_own)
+        if acc.keys is None:
+            acc.add(np.zeros(0, np.int32), 0)
+        row, col, cnt, val = acc.finalize(0)
+    else:
+        row, col, cnt, val = hip.cooccurrence(torch.from_numpy(ids).to(hip.device), len(tokens), context_size)
     row, col = row.cpu().numpy(), col.cpu().numpy()
     cnt, val = cnt.cpu().numpy(), val.cpu().numpy()
+    return interaction_columns(row, col, cnt, val, vocab, seed)
+
+
+def interaction_columns(row, col, cnt, val, vocab, seed=0) -> dict:
+    """The table's columns from (row, col, count, value): a seeded row permutation, the vocabulary joined in."""
+    tokens, counts, proportions = vocab
     perm = np.random.default_rng(seed).permutation(len(row))
     row, col, cnt, val = row[perm], col[perm], cnt[perm], val[perm]
     tok = np.asarray(tokens, dtype=object)
@@ -95,11 +118,13 @@ def create_glove_table(table: dict, count_minimum=10) -> dict:
     return out
 
 
-def process_data(text8: str, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, hip=None, seed=0):
+def process_data(text8: str, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, hip=None, seed=0,
+                 chunk_tokens=None):
     text_tokens = text8.split()
     vocab = create_vocabulary(text_tokens, vocab_size, coverage)
     logger.info("vocab created, size: %s.", len(vocab[0]))
-    table = create_interaction_table(token_ids(text_tokens, vocab[0]), vocab, context_size, hip=hip, seed=seed)
+    table = create_interaction_table(token_ids(text_tokens, vocab[0]), vocab, context_size, hip=hip, seed=seed,
+                                     chunk_tokens=chunk_tokens)
     logger.info("interaction table: %d pairs.", len(table["count"]))
     table = create_glove_table(table)
     logger.info("after the count filter: %d pairs.", len(table["count"]))
@@ -121,9 +146,9 @@ def save_data(data, save_dir=DATA_DIR):
     return data
 
 
-def main(url, dest, vocab_size, coverage, context_size, seed=0, **kwargs):
+def main(url, dest, vocab_size, coverage, context_size, seed=0, chunk_tokens=None, **kwargs):
     text8 = load_data(dest)
-    save_data(process_data(text8, vocab_size, coverage, context_size, seed=seed), dest)
+    save_data(process_data(text8, vocab_size, coverage, context_size, seed=seed, chunk_tokens=chunk_tokens), dest)
 
 
 if __name__ == "__main__":
@@ -136,6 +161,9 @@ if __name__ == "__main__":
     parser.add_argument("--coverage", type=float, default=COVERAGE, help="token coverage to set token count cutoff" + d)
     parser.add_argument("--context-size", type=int, default=CONTEXT_SIZE, help="size of context window" + d)
     parser.add_argument("--seed", type=int, default=0, help="seed of the row shuffle" + d)
+    parser.add_argument("--chunk-tokens", type=int, default=None,
+                        help="count the corpus in chunks of this many tokens, in bounded device memory (default: one call); a "
+                             "corpus too long to read whole: python -m trainer.cooccur")
     args = parser.parse_args()
     logger.info("call: %s.", " ".join(sys.argv))
     try:
