@@ -12,6 +12,7 @@
 //   rocPRIM scan      of the tile counts;
 //   merge_tiles<1>    the same walk with the counts beside the keys; outputs go to LDS at their rank and leave in 16-B stores.
 #include "glove_common.h"
+#include "glove_merge_path.h"
 #include "../../include/glove_cooc_stream_hip.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -20,9 +21,6 @@
 #include <rocprim/functional.hpp>
 
 namespace glove {
-
-constexpr uint64_t kNoKey = ~0ull;      // unused key slots hold the sentinel (sorts last)
-constexpr int64_t kMaxStateCap = (int64_t)1 << 40;
 
 // ---- chunk keys ------------------------------------------------------------------------------------------------------
 // slot layout of glove_cooc.hip: own position p has 2 context slots; partners may lie in the halo
@@ -95,24 +93,6 @@ constexpr int kTile = GLOVE_COOC_MERGE_TILE;      // merged positions per workgr
 constexpr int kVT = kTile / kBlock;               // ... per thread
 static_assert(kVT * kBlock == kTile && kVT == 8, "a thread walks 8 merged positions");
 
-// How many of the first `diag` entries of the merged order (ties to A) come from A.
-template <typename I>
-__device__ inline I merge_path(const uint64_t *__restrict__ A, I na, const uint64_t *__restrict__ B, I nb, I diag)
-{
-    I lo = diag > nb ? diag - nb : 0, hi = diag < na ? diag : na;
-    while (lo < hi) {
-        const I mid = (lo + hi) >> 1;
-        if (A[mid] <= B[diag - 1 - mid]) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ inline int64_t clamp_count(const int64_t *n, int64_t cap)
-{
-    const int64_t v = *n;
-    return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
 // split_a[t], split_b[t]: where tile t starts in A and in B.  Each input is duplicate-free, so a run of equal keys in the
 // merged order is one A entry followed by its B twin: a split that would fall between them moves one B entry forward.
 __global__ void merge_partition(const uint64_t *__restrict__ keys_a, const int64_t *__restrict__ n_a, int64_t cap_a,
@@ -128,36 +108,6 @@ __global__ void merge_partition(const uint64_t *__restrict__ keys_a, const int64
         split_a[t] = ai;
         split_b[t] = bi;
     }
-}
-
-// n 8-byte words from g to LDS / from LDS to g: 16 B per lane from the first 16-B aligned word on
-__device__ inline void load_words(const uint64_t *__restrict__ g, int n, uint64_t *s)
-{
-    const int head = (((uintptr_t)g & 15) != 0 && n > 0) ? 1 : 0;
-    const int pairs = (n - head) >> 1;
-    if (threadIdx.x == 0 && head) s[0] = g[0];
-    const ulonglong2 *g2 = (const ulonglong2 *)(g + head);
-    for (int p = threadIdx.x; p < pairs; p += kBlock) {
-        const ulonglong2 v = g2[p];
-        s[head + 2 * p] = v.x;
-        s[head + 2 * p + 1] = v.y;
-    }
-    if (threadIdx.x == 0 && ((n - head) & 1)) s[n - 1] = g[n - 1];
-}
-
-__device__ inline void store_words(uint64_t *__restrict__ g, int n, const uint64_t *s)
-{
-    const int head = (((uintptr_t)g & 15) != 0 && n > 0) ? 1 : 0;
-    const int pairs = (n - head) >> 1;
-    if (threadIdx.x == 0 && head) g[0] = s[0];
-    ulonglong2 *g2 = (ulonglong2 *)(g + head);
-    for (int p = threadIdx.x; p < pairs; p += kBlock) {
-        ulonglong2 v;
-        v.x = s[head + 2 * p];
-        v.y = s[head + 2 * p + 1];
-        g2[p] = v;
-    }
-    if (threadIdx.x == 0 && ((n - head) & 1)) g[n - 1] = s[n - 1];
 }
 
 // WRITE = false: count[tile] = the tile's number of output entries.  WRITE = true: the entries, at offset[tile].
@@ -368,12 +318,6 @@ static bool bad_key_shape(int32_t V, int32_t context)
 {
     if (V <= 0 || context <= 0 || context > 255) return true;
     return (double)V * (double)V * (double)context >= 9.0e18;      // key must fit 63 bits
-}
-
-static bool overlap(const void *p, size_t pn, const void *q, size_t qn)
-{
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
 }
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)

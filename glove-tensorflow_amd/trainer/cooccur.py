@@ -14,7 +14,13 @@ drawn over the FILTERED rows, where `trainer.text8` permutes all rows and filter
 in another order.  (`trainer.text8 --chunk-tokens` counts through the accumulator too and keeps its own order: its files
 are identical to its one-shot run's.)
 
-Vocabulary counting and id mapping are plain Python (`Counter`, `dict`) and pandas writes the CSV.
+Vocabulary counting and id mapping are plain Python (`Counter`, `dict`) by default.  `--tokenizer device` does both on
+the device (csrc/glove_text.hip, include/glove_text_hip.h) and writes the same files byte for byte: the file's raw bytes go
+up block by block; pass one tokenizes a block, makes its vocabulary (distinct 64-bit token hashes with counts and first
+occurrences) and merges it into the running one (`VocabAccumulator`); the host chooses the kept words from the counts
+alone and reads their strings back from the file; pass two tokenizes again, looks every token's hash up in the kept
+table, compares the bytes, and the ids go to `CoocAccumulator` without touching the host (`process_corpus`).  pandas
+writes the CSV.
 """
 from __future__ import annotations
 
@@ -56,14 +62,43 @@ def iter_token_blocks(path, block_bytes: int = BLOCK_BYTES):
         yield tokens
 
 
+def iter_byte_blocks(path, block_bytes: int = BLOCK_BYTES):
+    """The file as (offset, bytes) blocks of about `block_bytes` bytes, cut where `iter_token_blocks` cuts: behind the last
+    of the six ASCII separators, the rest carried into the next block.  So no token straddles two blocks, and no
+    multi-byte separator does (their bytes are all >= 0x80).  Concatenated, the blocks are the file; `offset` is the file
+    offset of a block's first byte.  The file is never read whole."""
+    carry, offset = b"", 0
+    with open(path, "rb") as f:
+        while True:
+            block = f.read(block_bytes)
+            if not block:
+                break
+            block = carry + block
+            if block[-1:].isspace():
+                carry = b""
+            else:
+                cut = max(block.rfind(c) for c in (b" ", b"\n", b"\t", b"\r", b"\x0b", b"\x0c"))
+                carry, block = block[cut + 1:], block[:cut + 1]
+            if block:
+                yield offset, block
+                offset += len(block)
+    if carry:
+        yield offset, carry
+
+
 def iter_chunks(id_blocks, chunk_tokens: int, context: int):
     """Cuts a stream of int32 id arrays into (ids[s : e + halo], e - s): chunks of `chunk_tokens` own positions, each
-    followed by its halo of min(context, tokens left) — what `CoocAccumulator.add` takes."""
+    followed by its halo of min(context, tokens left) — what `CoocAccumulator.add` takes.  Blocks that are device tensors
+    (the device tokenizer's) are cut the same way and stay where they are."""
     if chunk_tokens < 1:
         raise ValueError("chunk_tokens must be positive, got %d" % chunk_tokens)
     buf = np.zeros(0, np.int32)
     for ids in id_blocks:
-        buf = np.concatenate([buf, np.asarray(ids, np.int32)])
+        if hasattr(ids, "new_empty"):
+            import torch
+            buf = torch.cat([buf if hasattr(buf, "new_empty") else ids.new_empty(0), ids])
+        else:
+            buf = np.concatenate([buf, np.asarray(ids, np.int32)])
         while len(buf) >= chunk_tokens + context:       # the halo is complete
             yield buf[:chunk_tokens + context], chunk_tokens
             buf = buf[chunk_tokens:]
@@ -129,6 +164,136 @@ class CoocAccumulator:
         return self.backend.cooc_finalize(self.keys, self.counts, self.V, self.context, int(min_count))
 
 
+class VocabAccumulator:
+    """The vocabulary of a corpus that arrives in blocks of bytes, kept by the backend (on the device for GloveHip).  The
+    state is one table of distinct token hashes, ascending, with int64 counts and `where` words (first occurrence in the
+    file << 16 | token length); `add` tokenizes a block, makes its table and merges it in.  Two state buffers swap roles and
+    grow geometrically, as CoocAccumulator's do.
+
+    `backend` has the operations (GloveHip is the product one; the tests bring a NumPy one):
+        text_tokenize(block) -> (start, length, hashes, n_long)
+        text_block_vocab(hashes, start, length, base_offset) -> (keys, counts, where)
+        text_vocab_merge(keys_a, counts_a, where_a, keys_b, counts_b, where_b, keys_out, counts_out, where_out)
+            -> (keys, counts, where)    views of the outputs
+    A backend with a `device` gets the bytes moved there."""
+
+    def __init__(self, backend):
+        self.backend = backend
+        self.state = None                       # (keys, counts, where): views of the front buffers
+        self._front = self._back = None
+        self.blocks = self.tokens = self.n_long = 0
+
+    def __len__(self) -> int:
+        return 0 if self.state is None else len(self.state[0])
+
+    def add(self, block: bytes, offset: int):
+        """block: raw bytes that end behind a separator (or with the file); offset: the file offset of its first byte."""
+        start, length, hashes, n_long = self.backend.text_tokenize(_block_array(block, self.backend))
+        self.blocks += 1
+        self.tokens += len(hashes)
+        self.n_long += int(n_long)
+        new = self.backend.text_block_vocab(hashes, start, length, int(offset))
+        m = len(new[0])
+        if self.state is None:                  # the first block is the state (copied: views of a bigger buffer)
+            self._front = tuple(_resized(a, max(m, 1)) for a in new)
+            for buf, a in zip(self._front, new):
+                buf[:m] = a
+            self.state = tuple(buf[:m] for buf in self._front)
+            return
+        if m == 0:
+            return
+        need = len(self.state[0]) + m
+        if self._back is None or len(self._back[0]) < need:
+            cap = max(need, 2 * len(self._front[0]))
+            self._back = tuple(_resized(a, cap) for a in new)
+        self.state = tuple(self.backend.text_vocab_merge(*self.state, *new, *self._back))
+        self._front, self._back = self._back, self._front
+
+    def counts_and_where(self):
+        """(counts, where) of the distinct tokens as numpy int64 arrays (in hash order)."""
+        if self.state is None:
+            return np.zeros(0, np.int64), np.zeros(0, np.int64)
+        return tuple(np.asarray(a.cpu() if hasattr(a, "cpu") else a, np.int64) for a in self.state[1:])
+
+
+def _block_array(block: bytes, backend):
+    """A block's bytes as the uint8 array the backend takes (a device tensor where it has a `device`)."""
+    arr = np.frombuffer(block, np.uint8)
+    if hasattr(backend, "device"):
+        import torch
+        return torch.from_numpy(arr.copy()).to(backend.device)      # (the copy: torch wants a writable buffer)
+    return arr
+
+
+FNV_BASIS, FNV_PRIME, TEXT_MAX_TOKEN = 0xcbf29ce484222325, 0x100000001b3, 65535
+
+
+def token_hash(word: bytes) -> int:
+    """The device tokenizer's hash of a token (include/glove_text_hip.h): 64-bit FNV-1a over its first 65535 bytes,
+    all-ones replaced by all-ones - 1."""
+    h = FNV_BASIS
+    for c in word[:TEXT_MAX_TOKEN]:
+        h = ((h ^ c) * FNV_PRIME) & 0xFFFFFFFFFFFFFFFF
+    return h - 1 if h == 0xFFFFFFFFFFFFFFFF else h
+
+
+def kept_table(lookup: dict, backend=None):
+    """The table pass two searches, from the token -> id dict the Python path looks tokens up in: (hashes ascending, as
+    the int64 bit patterns of the uint64 values; ids int32; offsets int64 [n + 1]; the words' bytes, concatenated).  Two
+    kept words with one hash are a collision the device could not tell apart: ValueError."""
+    words = [(token_hash(tok.encode()), tok.encode(), i) for tok, i in lookup.items()]
+    words.sort(key=lambda w: w[0])
+    keys = np.asarray([w[0] for w in words], np.uint64)
+    if len(keys) > 1 and (keys[1:] == keys[:-1]).any():
+        raise ValueError("%d kept words share their 64-bit hash with another kept word: run with --tokenizer python"
+                         % int(2 * (keys[1:] == keys[:-1]).sum()))
+    ids = np.asarray([w[2] for w in words], np.int32)
+    off = np.zeros(len(words) + 1, np.int64)
+    np.cumsum(np.asarray([len(w[1]) for w in words], np.int64), out=off[1:])
+    data = np.frombuffer(b"".join(w[1] for w in words), np.uint8)
+    arrays = (keys.view(np.int64), ids, off, data)
+    if hasattr(backend, "device"):
+        import torch
+        return tuple(torch.from_numpy(a.copy()).to(backend.device) for a in arrays)
+    return arrays
+
+
+def device_vocabulary(path, vocab_size, coverage, backend, block_bytes: int = BLOCK_BYTES):
+    """Pass one of the device tokenizer: text8.vocabulary_from_counts(count_vocabulary(path)), the strings of the kept
+    tokens read back from the file at the offsets the device returns."""
+    from trainer import text8
+    acc = VocabAccumulator(backend)
+    for offset, block in iter_byte_blocks(path, block_bytes):
+        acc.add(block, offset)
+    if acc.n_long:
+        raise ValueError("%d tokens are longer than %d bytes, beyond what the device tokenizer hashes: run with "
+                         "--tokenizer python" % (acc.n_long, TEXT_MAX_TOKEN))
+    counts, where = acc.counts_and_where()
+    logger.info("%d tokens, %d distinct, in %d blocks.", acc.tokens, len(counts), acc.blocks)
+    with open(path, "rb") as f:
+        def read_token(w):
+            f.seek(w >> 16)
+            return f.read(w & 0xFFFF).decode()
+        return text8.vocabulary_from_arrays(counts, where, read_token, vocab_size, coverage)
+
+
+def device_id_blocks(path, lookup, backend, block_bytes: int = BLOCK_BYTES):
+    """Pass two of the device tokenizer: the ids of every block's tokens, as the backend's arrays (device tensors for
+    GloveHip: they feed CoocAccumulator.add through iter_chunks without touching the host)."""
+    kept = kept_table(lookup, backend)
+    for _, block in iter_byte_blocks(path, block_bytes):
+        data = _block_array(block, backend)
+        start, length, hashes, n_long = backend.text_tokenize(data)
+        ids, n_mismatch = backend.text_token_ids(data, start, length, hashes, kept)
+        if n_long:
+            raise ValueError("%d tokens are longer than %d bytes: run with --tokenizer python" % (n_long, TEXT_MAX_TOKEN))
+        if n_mismatch:
+            raise ValueError("%d tokens share a 64-bit hash with a kept word of other bytes (a hash collision): run with "
+                             "--tokenizer python" % n_mismatch)
+        if len(ids):
+            yield ids
+
+
 def count_vocabulary(path, block_bytes: int = BLOCK_BYTES) -> Counter:
     """Pass one: the running token counts of the corpus (first occurrences in corpus order, as Counter(text.split()))."""
     counter = Counter()
@@ -138,18 +303,36 @@ def count_vocabulary(path, block_bytes: int = BLOCK_BYTES) -> Counter:
 
 
 def process_corpus(path, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, chunk_tokens=CHUNK_TOKENS,
-                   count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES):
-    """The data `trainer.text8.save_data` writes, from a corpus file of any length."""
+                   count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python"):
+    """The data `trainer.text8.save_data` writes, from a corpus file of any length.
+
+    tokenizer="python" counts the vocabulary and maps tokens to ids on the host (`Counter`, `dict`); "device" does both on
+    the backend (include/glove_text_hip.h) and returns the same data.  Why it is the same whenever it returns (it raises
+    ValueError where the device counts a token longer than 65535 bytes or a hash mismatch, naming the count): the device
+    keeps one entry per distinct 64-bit token hash, so two distinct words can share an entry only if their hashes collide.
+    If the merged entry is kept, the table of pass two holds the bytes of the word that occurred first, and pass two sees
+    that the other word's bytes differ: a mismatch, counted.  If it is not kept, both words are out of vocabulary in
+    either path, and an entry below the cutoff moves neither the cutoff nor the ranks of the kept entries.
+    Invalid UTF-8 is the one input on which the paths differ: Python raises UnicodeDecodeError at the block that holds it,
+    the device path only where a kept word does not decode."""
     from trainer import text8
+    if tokenizer not in ("python", "device"):
+        raise ValueError("tokenizer must be 'python' or 'device', got %r" % (tokenizer,))
     if backend is None:
         from trainer.hip_api import GloveHip
         backend = GloveHip("cuda:0")
-    vocab = text8.vocabulary_from_counts(count_vocabulary(path, block_bytes), vocab_size, coverage)
+    if tokenizer == "device":
+        vocab = device_vocabulary(path, vocab_size, coverage, backend, block_bytes)
+    else:
+        vocab = text8.vocabulary_from_counts(count_vocabulary(path, block_bytes), vocab_size, coverage)
     logger.info("vocab created, size: %s.", len(vocab[0]))
     lookup = {tok: i for i, tok in enumerate(vocab[0])}
     acc = CoocAccumulator(len(vocab[0]), context_size, backend)
-    id_blocks = (np.fromiter((lookup.get(t, 0) for t in tokens), dtype=np.int32, count=len(tokens))
-                 for tokens in iter_token_blocks(path, block_bytes))
+    if tokenizer == "device":
+        id_blocks = device_id_blocks(path, lookup, backend, block_bytes)
+    else:
+        id_blocks = (np.fromiter((lookup.get(t, 0) for t in tokens), dtype=np.int32, count=len(tokens))
+                     for tokens in iter_token_blocks(path, block_bytes))
     for piece, n_own in iter_chunks(id_blocks, chunk_tokens, context_size):
         acc.add(piece, n_own)
         logger.info("chunk %d: %d keys in the state.", acc.chunks, len(acc))
@@ -162,9 +345,10 @@ def process_corpus(path, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=
 
 
 def main(corpus, dest, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, chunk_tokens=CHUNK_TOKENS,
-         count_minimum=10, seed=0, backend=None, **kwargs):
+         count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python", **kwargs):
     from trainer import text8
-    data = process_corpus(corpus, vocab_size, coverage, context_size, chunk_tokens, count_minimum, seed, backend=backend)
+    data = process_corpus(corpus, vocab_size, coverage, context_size, chunk_tokens, count_minimum, seed, backend=backend,
+                          block_bytes=block_bytes, tokenizer=tokenizer)
     return text8.save_data(data, dest)
 
 
@@ -180,6 +364,9 @@ if __name__ == "__main__":
     parser.add_argument("--chunk-tokens", type=int, default=CHUNK_TOKENS, help="corpus positions counted per chunk" + d)
     parser.add_argument("--count-minimum", type=int, default=10, help="pairs seen less often are dropped" + d)
     parser.add_argument("--seed", type=int, default=0, help="seed of the row shuffle" + d)
+    parser.add_argument("--tokenizer", choices=("python", "device"), default="python",
+                        help="where the corpus is split into tokens, counted and numbered: on the host, or on the GPU from "
+                             "the file's bytes (the same files)" + d)
     args = parser.parse_args()
     logger.info("call: %s.", " ".join(sys.argv))
     try:

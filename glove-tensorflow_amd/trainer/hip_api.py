@@ -1,5 +1,6 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
-include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and of libglove_prep_hip.so (include/glove_cooc_stream_hip.h).
+include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
+include/glove_text_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -32,6 +33,9 @@ GLOVE_EVAL_SIM_ABI_VERSION = 1      # include/glove_eval_sim_hip.h: the same lib
 GLOVE_EVAL_CLUSTER_ABI_VERSION = 1  # include/glove_eval_cluster_hip.h: the third header (spherical k-means), likewise
 GLOVE_COOC_STREAM_ABI_VERSION = 1   # include/glove_cooc_stream_hip.h (libglove_prep_hip.so)
 COOC_MERGE_TILE = 2048              # GLOVE_COOC_MERGE_TILE: merged positions one workgroup of glove_cooc_merge_u64 owns
+GLOVE_TEXT_ABI_VERSION = 1          # include/glove_text_hip.h: the same library's second header (tokenizing), versioned on its own
+TEXT_TILE_BYTES = 4096              # GLOVE_TEXT_TILE_BYTES: bytes of a block one workgroup of glove_text_tokenize_u8 owns
+TEXT_MAX_TOKEN = 65535              # GLOVE_TEXT_MAX_TOKEN: bytes of a token its hash covers; the longest length a `where` word holds
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
 ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
@@ -85,6 +89,10 @@ KMEANS_MAX_CLUSTERS = 4096
 PREP_EXPORTED_SYMBOLS = ("glove_cooc_stream_abi_version", "glove_cooc_chunk_workspace_bytes", "glove_cooc_chunk_keys_i32",
                          "glove_cooc_merge_workspace_bytes", "glove_cooc_merge_u64", "glove_cooc_finalize_workspace_bytes",
                          "glove_cooc_finalize")
+# every symbol include/glove_text_hip.h declares (the same library)
+TEXT_EXPORTED_SYMBOLS = ("glove_text_abi_version", "glove_text_tokenize_workspace_bytes", "glove_text_tokenize_u8",
+                         "glove_text_block_vocab_workspace_bytes", "glove_text_block_vocab",
+                         "glove_text_vocab_merge_workspace_bytes", "glove_text_vocab_merge", "glove_text_token_ids_i32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -251,7 +259,7 @@ _prep_lib = None
 
 
 def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h) and declare the prototypes, at the first call that needs
+    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h) and declare the prototypes, at the first call that needs
     it: training never loads it.  Raises if it is not built, like load_library."""
     global _prep_lib
     if _prep_lib is not None and path is None:
@@ -265,11 +273,22 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_cooc_merge_u64": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp, sz, vp]),
         "glove_cooc_finalize_workspace_bytes": (sz, [i64]),
         "glove_cooc_finalize": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_text_abi_version": (C.c_int, []),
+        "glove_text_tokenize_workspace_bytes": (sz, [i64]),
+        "glove_text_tokenize_u8": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_text_block_vocab_workspace_bytes": (sz, [i64]),
+        "glove_text_block_vocab": (C.c_int, [vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_text_vocab_merge_workspace_bytes": (sz, [i64, i64]),
+        "glove_text_vocab_merge": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_text_token_ids_i32": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp]),
     }
     lib = _open(Path(path) if path else PREP_LIB_PATH, protos)
     if lib.glove_cooc_stream_abi_version() != GLOVE_COOC_STREAM_ABI_VERSION:
         raise GloveHipError("ABI mismatch: prep library %d, binding %d"
                             % (lib.glove_cooc_stream_abi_version(), GLOVE_COOC_STREAM_ABI_VERSION))
+    if lib.glove_text_abi_version() != GLOVE_TEXT_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: prep library (text entry points) %d, binding %d"
+                            % (lib.glove_text_abi_version(), GLOVE_TEXT_ABI_VERSION))
     if path is None:
         _prep_lib = lib
     return lib
@@ -1527,3 +1546,110 @@ class GloveHip:
         if m > cap:
             raise GloveHipError("co-occurrence table has %d entries, capacity %d" % (m, cap))
         return row[:m], col[:m], cnt[:m], val[:m]
+
+    # ---- tokenizing and numbering a corpus (include/glove_text_hip.h): what trainer.cooccur drives with --tokenizer device.
+    # Hashes and vocabulary keys travel as int64 tensors whose bits are the header's uint64.
+    def text_tokenize_enqueue(self, block, start, length, hashes, n_tokens, n_long, ws=None):
+        """glove_text_tokenize_u8 on the current stream, nothing read back: block uint8 [n_bytes]; start / length int32
+        [cap], hashes int64 [cap]; n_tokens and n_long int64 device tensors ([>= 2] each where the block may be empty)."""
+        lib = load_prep_library()
+        _require(block, torch.uint8); _require(start, torch.int32); _require(length, torch.int32, int(start.numel()))
+        _require(hashes, torch.int64, int(start.numel())); _require(n_tokens, torch.int64); _require(n_long, torch.int64)
+        n_bytes = int(block.numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_text_tokenize_workspace_bytes(n_bytes), "glove_text_tokenize_workspace_bytes")
+        _check(lib.glove_text_tokenize_u8(_ptr(block) if n_bytes else None, n_bytes, _ptr(start), _ptr(length), _ptr(hashes),
+                                          _ptr(n_tokens), _ptr(n_long), int(start.numel()), _ptr(ws), ws.numel(), _stream()),
+               "glove_text_tokenize_u8")
+
+    def text_block_vocab_enqueue(self, hashes, start, length, n_tokens, base_offset: int, keys, counts, where, n_out, ws=None):
+        """glove_text_block_vocab on the current stream, nothing read back; n_tokens int64 [>= 1], n_out int64 [>= 2]."""
+        lib = load_prep_library()
+        cap_tokens, cap_out = int(hashes.numel()), int(keys.numel())
+        _require(hashes, torch.int64); _require(start, torch.int32, cap_tokens); _require(length, torch.int32, cap_tokens)
+        _require(keys, torch.int64); _require(counts, torch.int64, cap_out); _require(where, torch.int64, cap_out)
+        _require(n_tokens, torch.int64); _require(n_out, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_text_block_vocab_workspace_bytes(cap_tokens), "glove_text_block_vocab_workspace_bytes")
+        _check(lib.glove_text_block_vocab(_ptr(hashes), _ptr(start), _ptr(length), _ptr(n_tokens), cap_tokens, int(base_offset),
+                                          _ptr(keys), _ptr(counts), _ptr(where), _ptr(n_out), cap_out, _ptr(ws), ws.numel(),
+                                          _stream()), "glove_text_block_vocab")
+
+    def text_vocab_merge_enqueue(self, a, n_a, b, n_b, out, n_out, ws=None):
+        """glove_text_vocab_merge on the current stream, nothing read back: a, b, out are (keys, counts, where) triples of
+        int64 tensors, n_a, n_b, n_out int64 device tensors."""
+        lib = load_prep_library()
+        for triple in (a, b, out):
+            for t in triple:
+                _require(t, torch.int64, int(triple[0].numel()))
+        for t in (n_a, n_b, n_out):
+            _require(t, torch.int64)
+        cap_a, cap_b = int(a[0].numel()), int(b[0].numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_text_vocab_merge_workspace_bytes(cap_a, cap_b), "glove_text_vocab_merge_workspace_bytes")
+        _check(lib.glove_text_vocab_merge(_ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(n_a), cap_a, _ptr(b[0]), _ptr(b[1]), _ptr(b[2]),
+                                          _ptr(n_b), cap_b, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(n_out),
+                                          int(out[0].numel()), _ptr(ws), ws.numel(), _stream()), "glove_text_vocab_merge")
+
+    def text_token_ids_enqueue(self, block, start, length, hashes, n_tokens, kept, ids, n_mismatch):
+        """glove_text_token_ids_i32 on the current stream, nothing read back: kept = (keys int64 [n_kept] ascending as
+        uint64, ids int32 [n_kept], offsets int64 [n_kept + 1], bytes uint8); ids int32 [cap]; n_mismatch int64 [>= 2]."""
+        lib = load_prep_library()
+        kept_keys, kept_id, kept_off, kept_bytes = kept
+        cap, n_kept = int(hashes.numel()), int(kept_keys.numel())
+        _require(block, torch.uint8); _require(hashes, torch.int64); _require(start, torch.int32, cap)
+        _require(length, torch.int32, cap); _require(ids, torch.int32, cap); _require(n_tokens, torch.int64)
+        _require(kept_keys, torch.int64); _require(kept_id, torch.int32, n_kept); _require(kept_off, torch.int64, n_kept + 1)
+        _require(kept_bytes, torch.uint8); _require(n_mismatch, torch.int64)
+        _check(lib.glove_text_token_ids_i32(_ptr(block) if block.numel() else None, int(block.numel()), _ptr(start), _ptr(length),
+                                            _ptr(hashes), _ptr(n_tokens), cap, _ptr(kept_keys) if n_kept else None,
+                                            _ptr(kept_id) if n_kept else None, _ptr(kept_off),
+                                            _ptr(kept_bytes) if n_kept else None, n_kept, _ptr(ids), _ptr(n_mismatch), _stream()),
+               "glove_text_token_ids_i32")
+
+    def text_tokenize(self, block: torch.Tensor):
+        """(start int32, length int32, hashes int64, n_long): the whitespace-separated tokens of a block of bytes, in order
+        (one host sync for the sizes).  n_long: tokens longer than TEXT_MAX_TOKEN bytes, which their hash does not cover."""
+        cap = (int(block.numel()) + 1) // 2         # the most tokens the bytes can hold
+        start = torch.empty(cap, dtype=torch.int32, device=block.device)
+        length = torch.empty_like(start)
+        hashes = torch.empty(cap, dtype=torch.int64, device=block.device)
+        sizes = torch.zeros(4, dtype=torch.int64, device=block.device)
+        self.text_tokenize_enqueue(block, start, length, hashes, sizes[0:2], sizes[2:4])
+        m, n_long = (int(v) for v in sizes[0:3:2].tolist())
+        return start[:m], length[:m], hashes[:m], n_long
+
+    def text_block_vocab(self, hashes, start, length, base_offset: int = 0):
+        """(keys, counts, where) of a block's tokens: the distinct hashes ascending (as uint64), how often each occurred,
+        and ((base_offset + start of the first occurrence) << 16) | min(length, TEXT_MAX_TOKEN).  One host sync."""
+        n = int(hashes.numel())
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=hashes.device)
+        counts, where = torch.empty_like(keys), torch.empty_like(keys)
+        sizes = torch.tensor([n, 0, 0], dtype=torch.int64).to(hashes.device)
+        self.text_block_vocab_enqueue(hashes, start, length, sizes[0:1], base_offset, keys, counts, where, sizes[1:3])
+        m = int(sizes[1].item())
+        return keys[:m], counts[:m], where[:m]
+
+    def text_vocab_merge(self, keys_a, counts_a, where_a, keys_b, counts_b, where_b, keys_out=None, counts_out=None,
+                         where_out=None):
+        """The ascending union of two vocabularies, counts summed and the smaller `where` kept for shared keys ->
+        (keys, counts, where), views of the outputs (default: fresh ones that hold both inputs).  One host sync."""
+        n_a, n_b = int(keys_a.numel()), int(keys_b.numel())
+        if keys_out is None:
+            keys_out = torch.empty(max(1, n_a + n_b), dtype=torch.int64, device=keys_a.device)
+            counts_out, where_out = torch.empty_like(keys_out), torch.empty_like(keys_out)
+        sizes = torch.tensor([n_a, n_b, 0, 0], dtype=torch.int64).to(keys_a.device)
+        self.text_vocab_merge_enqueue((keys_a, counts_a, where_a), sizes[0:1], (keys_b, counts_b, where_b), sizes[1:2],
+                                      (keys_out, counts_out, where_out), sizes[2:4])
+        m = int(sizes[2].item())
+        if m > keys_out.numel():
+            raise GloveHipError("the merged vocabulary has %d keys, capacity %d" % (m, keys_out.numel()))
+        return keys_out[:m], counts_out[:m], where_out[:m]
+
+    def text_token_ids(self, block, start, length, hashes, kept):
+        """(ids int32, n_mismatch): every token's id from the kept table (see text_token_ids_enqueue), 0 where its hash
+        is not kept; n_mismatch counts tokens whose hash is kept but whose bytes are another word's (one host sync)."""
+        ids = torch.empty(int(hashes.numel()), dtype=torch.int32, device=hashes.device)
+        sizes = torch.tensor([int(hashes.numel()), 0, 0], dtype=torch.int64).to(hashes.device)
+        self.text_token_ids_enqueue(block, start, length, hashes, sizes[0:1], kept, ids, sizes[1:3])
+        return ids, int(sizes[1].item())

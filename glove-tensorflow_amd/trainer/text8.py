@@ -61,6 +61,26 @@ def vocabulary_from_counts(counter: Counter, vocab_size=VOCAB_SIZE, coverage=COV
     return tokens, counts, counts / total
 
 
+def vocabulary_from_arrays(counts, where, read_token, vocab_size=VOCAB_SIZE, coverage=COVERAGE):
+    """vocabulary_from_counts from arrays: counts[i] of distinct token i and where[i], a number that orders the tokens by
+    their first occurrence in the corpus (what the device tokenizer of trainer.cooccur returns).  `read_token(where[i])`
+    gives the token's string and is called for the kept tokens only.  Count descending, ties by first occurrence: the
+    order of Counter.most_common."""
+    counts, where = np.asarray(counts, np.int64), np.asarray(where, np.int64)
+    by_count = np.sort(counts)[::-1]
+    total = int(by_count.sum())
+    cutoff = by_count[np.searchsorted(np.cumsum(by_count) / total, coverage)]
+    order = np.lexsort((where, -counts))[:vocab_size]
+    order = order[counts[order] >= cutoff]
+    kept = counts[order]
+    tokens = ["<UNK>"] + [read_token(int(w)) for w in where[order]]
+    counts = np.concatenate([np.asarray([total - int(kept.sum())], np.int64), kept])
+    order = np.argsort(-counts, kind="stable")        # ties keep most_common order
+    tokens = [tokens[i] for i in order]
+    counts = counts[order]
+    return tokens, counts, counts / total
+
+
 def token_ids(text_tokens, vocab_tokens) -> np.ndarray:
     """id = position in the vocabulary, out-of-vocabulary -> 0 (text8.py:85-86)."""
     lookup = {tok: i for i, tok in enumerate(vocab_tokens)}
