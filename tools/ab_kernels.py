@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """In-process A/B timing of kernel variants (cdna guide rule 24: interleaved rounds, one process).
-Usage: python tools/ab_kernels.py [--workload text8_d64] [--batch-size 131072] [--caps 32,16]"""
+Usage: python tools/ab_kernels.py [--workload text8_d64] [--batch-size 131072] [--caps 32,16]
+The one-launch step of two builds, timed and compared bit for bit:
+  python tools/ab_kernels.py --batch-size 1024 --caps 16 --tags --step-form 5 [--optimizer Adam] --only step --libs a.so,b.so --check"""
 import argparse
 import ctypes as C
 import statistics
@@ -24,6 +26,8 @@ def main():
     ap.add_argument("--step-form", type=int, default=0)
     ap.add_argument("--only", default="", help="comma-separated subset of rowpass,colpass,passes,apply,step")
     ap.add_argument("--twin", action="store_true", help="twinned row table (step form 4 under auto)")
+    ap.add_argument("--tags", action="store_true", help="twinned, step-tagged tables (DeviceTables.enable_tags: the one-launch step, form 5)")
+    ap.add_argument("--optimizer", default="Adagrad", choices=["Adagrad", "Adam"], help="Adam: only the whole step (--only step)")
     ap.add_argument("--batches", type=int, default=8, help="resident batches cycled through (1: the plan stays cache-warm)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--reps", type=int, default=40)
@@ -36,10 +40,19 @@ def main():
     wl = synthetic.make_workload(args.workload, device=dev, work_device=dev)
     V, d, B = wl["V"], wl["d"], args.batch_size
     nb = min(args.batches, wl["row"].numel() // B)
-    tables = DeviceTables(V, d, "Adagrad", device=dev, seed=1)
-    if args.twin:
-        tables.enable_twin()
-    hyper = make_hyper(learning_rate=0.05, batch_size=B, step_form=args.step_form)
+    if args.optimizer != "Adagrad" and args.only != "step":
+        ap.error("--optimizer %s times the whole step alone: --only step" % args.optimizer)
+
+    def make_tables():
+        t = DeviceTables(V, d, args.optimizer, device=dev, seed=1)
+        if args.twin:
+            t.enable_twin()
+        if args.tags:
+            t.enable_tags()
+        return t, (hip.dense_grad_buffer(t) if args.optimizer == "Adam" else None)
+
+    tables, G = make_tables()
+    hyper = make_hyper(learning_rate=0.05 if args.optimizer == "Adagrad" else 0.001, batch_size=B, step_form=args.step_form)
     loss = torch.zeros(4, device=dev)
     configs = []
     for cap in [int(c) for c in args.caps.split(",")]:
@@ -58,7 +71,7 @@ def main():
                       "passes": lambda p: hip.passes(p, tables, hyper, ws),
                       "colpass": lambda p: hip.colpass(p, tables, hyper, ws),
                       "apply": lambda p: hip.apply_adagrad(p, tables, hyper, loss, ws),
-                      "step": lambda p: hip.step_adagrad(p, tables, hyper, loss, ws)}[name]
+                      "step": lambda p: hip.step(p, tables, hyper, G, loss, ws)}[name]
                 for i in range(4):
                     fn(plans[i % nb])
                 a, b = ev(), ev()
@@ -72,16 +85,16 @@ def main():
     if args.check:
         outs = []
         for v in range(len(hips)):
-            t2 = DeviceTables(V, d, "Adagrad", device=dev, seed=1)
-            if args.twin:
-                t2.enable_twin()
+            t2, G2 = make_tables()
             plans = [c[2] for c in configs if c[1] == v][0]
             for b in range(min(nb, 2)):
-                hips[v].step_adagrad(plans[b], t2, hyper, loss, ws)
+                hips[v].step(plans[b], t2, hyper, G2, loss, ws)
             torch.cuda.synchronize()
-            outs.append([x.clone() for x in (t2.R, t2.C, t2.br, t2.bc, t2.s1["R"], t2.s1["C"], loss)])
+            slots = [(k + "_" + n, s[n]) for k, s in (("s1", t2.s1), ("s2", t2.s2)) if s for n in t2.NAMES]
+            outs.append([(k, x.clone()) for k, x in [(n, getattr(t2, n)) for n in t2.NAMES] + slots + [("scalars", t2.scalars), ("loss", loss)]])
         for v in range(1, len(hips)):
-            print("check lib=%s vs %s: max |diff| %s" % (libs[v], libs[0], ["%.3g" % (a - b).abs().max().item() for a, b in zip(outs[0], outs[v])]))
+            print("check lib=%s vs %s: max |diff| %s" % (libs[v], libs[0], " ".join("%s %.3g" % (k, (a - b).abs().max().item())
+                                                                                       for (k, a), (_, b) in zip(outs[0], outs[v]))))
     print("%s B=%d d=%d  (us per launch incl. launch gaps; median / min over %d rounds)" % (args.workload, B, d, args.rounds))
     for (cap, v), r in res.items():
         print("cap=%-3d lib=%s  " % (cap, libs[v] or "shipped") + "  ".join(
