@@ -1,6 +1,6 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
-include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
-include/glove_text_hip.h).
+include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h), of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
+include/glove_text_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -26,6 +26,7 @@ LIB_PATH = PKG_DIR / "lib" / "libglove_hip.so"
 EVAL_LIB_PATH = PKG_DIR / "lib" / "libglove_eval_hip.so"      # include/glove_eval_hip.h: scoring finished embeddings, a library of its own
 
 PREP_LIB_PATH = PKG_DIR / "lib" / "libglove_prep_hip.so"      # include/glove_cooc_stream_hip.h: counting a corpus chunk by chunk, a library of its own
+FACTOR_LIB_PATH = PKG_DIR / "lib" / "libglove_factor_hip.so"  # include/glove_factor_hip.h: the count-based baselines (trainer.svd), a library of its own
 
 GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
@@ -36,6 +37,9 @@ COOC_MERGE_TILE = 2048              # GLOVE_COOC_MERGE_TILE: merged positions on
 GLOVE_TEXT_ABI_VERSION = 1          # include/glove_text_hip.h: the same library's second header (tokenizing), versioned on its own
 TEXT_TILE_BYTES = 4096              # GLOVE_TEXT_TILE_BYTES: bytes of a block one workgroup of glove_text_tokenize_u8 owns
 TEXT_MAX_TOKEN = 65535              # GLOVE_TEXT_MAX_TOKEN: bytes of a token its hash covers; the longest length a `where` word holds
+GLOVE_FACTOR_ABI_VERSION = 1        # include/glove_factor_hip.h (libglove_factor_hip.so)
+FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one lane group of glove_csr_spmm_f32 sums
+REWEIGHT_KINDS = {"none": 0, "sqrt": 1, "log1p": 2, "ppmi": 3}      # GLOVE_REWEIGHT_*
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
 ROW_WISE_OPTIMIZERS = names(lambda o: o.row_wise)      # slot 1 of R and C is ONE float per row (float[rows]), not shaped like the table
@@ -93,6 +97,9 @@ PREP_EXPORTED_SYMBOLS = ("glove_cooc_stream_abi_version", "glove_cooc_chunk_work
 TEXT_EXPORTED_SYMBOLS = ("glove_text_abi_version", "glove_text_tokenize_workspace_bytes", "glove_text_tokenize_u8",
                          "glove_text_block_vocab_workspace_bytes", "glove_text_block_vocab",
                          "glove_text_vocab_merge_workspace_bytes", "glove_text_vocab_merge", "glove_text_token_ids_i32")
+# every symbol include/glove_factor_hip.h declares (libglove_factor_hip.so)
+FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace_bytes", "glove_csr_spmm_f32",
+                           "glove_csr_row_sums_f64", "glove_coo_reweight_f32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -291,6 +298,36 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
                             % (lib.glove_text_abi_version(), GLOVE_TEXT_ABI_VERSION))
     if path is None:
         _prep_lib = lib
+    return lib
+
+
+_factor_lib = None
+
+
+def factor_prototypes() -> dict:
+    """name -> (result, arguments) of every function include/glove_factor_hip.h declares."""
+    sz, i32, i64, vp, f64 = C.c_size_t, C.c_int32, C.c_int64, C.c_void_p, C.c_double
+    return {
+        "glove_factor_abi_version": (C.c_int, []),
+        "glove_csr_spmm_workspace_bytes": (sz, [i32, i64, i32]),
+        "glove_csr_spmm_f32": (C.c_int, [vp, vp, vp, i32, i32, i64, vp, i32, vp, vp, sz, vp]),
+        "glove_csr_row_sums_f64": (C.c_int, [vp, vp, i32, i64, vp, vp, sz, vp]),
+        "glove_coo_reweight_f32": (C.c_int, [vp, vp, vp, i64, i32, vp, vp, f64, f64, vp, vp]),
+    }
+
+
+def load_factor_library(path: os.PathLike | None = None) -> C.CDLL:
+    """dlopen libglove_factor_hip.so (include/glove_factor_hip.h) and declare the prototypes, at the first call that needs
+    it: training never loads it.  Raises if it is not built, like load_library."""
+    global _factor_lib
+    if _factor_lib is not None and path is None:
+        return _factor_lib
+    lib = _open(Path(path) if path else FACTOR_LIB_PATH, factor_prototypes())
+    if lib.glove_factor_abi_version() != GLOVE_FACTOR_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: factor library %d, binding %d"
+                            % (lib.glove_factor_abi_version(), GLOVE_FACTOR_ABI_VERSION))
+    if path is None:
+        _factor_lib = lib
     return lib
 
 
@@ -1434,6 +1471,67 @@ class GloveHip:
             if best is None or objective > best.objective:
                 best = KMeansResult(assign, cos, cents, t, converged, objective, objectives, assignments)
         return best
+
+    # ---- count-based baselines (include/glove_factor_hip.h): what trainer.svd drives
+    def _csr_args(self, row_ptr, col_idx, val, n_rows: int):
+        _require(row_ptr, torch.int64, n_rows + 1); _require(val, torch.float32)
+        nnz = int(val.numel())
+        if col_idx is not None:
+            _require(col_idx, torch.int32, nnz)
+        return nnz
+
+    def csr_spmm(self, row_ptr: torch.Tensor, col_idx: torch.Tensor, val: torch.Tensor, n_rows: int, n_cols: int,
+                 B: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
+        """Y [n_rows, l] = A B for the CSR matrix A (row_ptr int64 [n_rows + 1] from 0 to nnz, col_idx int32, val float32)
+        and B [n_cols, l] float32, l % 4 == 0 up to 1024.  Bitwise repeatable (a fixed summation order, no float
+        atomics); a row without nonzeros comes back as zeros.  The columns must lie in [0, n_cols)."""
+        nnz = self._csr_args(row_ptr, col_idx, val, n_rows)
+        _require(B, torch.float32)
+        if B.dim() != 2 or B.shape[0] != n_cols:
+            raise GloveHipError("expected B [n_cols = %d, l], got %s" % (n_cols, tuple(B.shape)))
+        lib, l = load_factor_library(), int(B.shape[1])
+        need = lib.glove_csr_spmm_workspace_bytes(n_rows, nnz, l)
+        if need == 0 or l == 0:
+            raise GloveHipError("csr_spmm takes 1 <= n_rows, nnz <= 2^31 - 1 and l %% 4 == 0 in [4, 1024]: got n_rows = %d, "
+                                "nnz = %d, l = %d" % (n_rows, nnz, l))
+        ws = torch.empty(need, dtype=torch.uint8, device=B.device) if ws is None else ws
+        Y = torch.empty(n_rows, l, dtype=torch.float32, device=B.device)
+        _check(lib.glove_csr_spmm_f32(_ptr(row_ptr), _ptr(col_idx), _ptr(val), n_rows, n_cols, nnz, _ptr(B), l, _ptr(Y),
+                                      _ptr(ws), ws.numel(), _stream()), "glove_csr_spmm_f32")
+        return Y
+
+    def csr_row_sums(self, row_ptr: torch.Tensor, val: torch.Tensor, n_rows: int) -> torch.Tensor:
+        """The sum of every CSR row's values in float64 [n_rows] (the marginals), in a fixed order."""
+        nnz = self._csr_args(row_ptr, None, val, n_rows)
+        lib = load_factor_library()
+        need = lib.glove_csr_spmm_workspace_bytes(n_rows, nnz, 0)
+        if need == 0:
+            raise GloveHipError("csr_row_sums takes 1 <= n_rows and nnz <= 2^31 - 1: got n_rows = %d, nnz = %d" % (n_rows, nnz))
+        ws = torch.empty(need, dtype=torch.uint8, device=val.device)
+        sums = torch.empty(n_rows, dtype=torch.float64, device=val.device)
+        _check(lib.glove_csr_row_sums_f64(_ptr(row_ptr), _ptr(val), n_rows, nnz, _ptr(sums), _ptr(ws), ws.numel(), _stream()),
+               "glove_csr_row_sums_f64")
+        return sums
+
+    def coo_reweight(self, row: torch.Tensor, col: torch.Tensor, val: torch.Tensor, kind: str, row_sums=None,
+                     col_weights=None, total: float = 0.0, log_shift: float = 0.0, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The entrywise transform `kind` (none, sqrt, log1p, ppmi) of a COO table's float32 values, computed in float64:
+        ppmi is max(0, log(x total / (row_sums[row] col_weights[col])) - log_shift) with float64 marginals.  `out` may be
+        `val` itself.  The ids must index the marginals: the kernel does not look."""
+        if kind not in REWEIGHT_KINDS:
+            raise GloveHipError("kind must be one of %s, got %r" % (", ".join(REWEIGHT_KINDS), kind))
+        _require(val, torch.float32)
+        nnz = int(val.numel())
+        _require(row, torch.int32, nnz); _require(col, torch.int32, nnz)
+        _require(row_sums, torch.float64); _require(col_weights, torch.float64)
+        if kind == "ppmi" and (row is None or col is None or row_sums is None or col_weights is None):
+            raise GloveHipError("ppmi needs row, col, row_sums and col_weights")
+        out = torch.empty_like(val) if out is None else out
+        _require(out, torch.float32, nnz)
+        _check(load_factor_library().glove_coo_reweight_f32(_ptr(row), _ptr(col), _ptr(val), nnz, REWEIGHT_KINDS[kind],
+                                                            _ptr(row_sums), _ptr(col_weights), float(total), float(log_shift),
+                                                            _ptr(out), _stream()), "glove_coo_reweight_f32")
+        return out
 
     # ---- data prep
     def cooccurrence(self, tokens: torch.Tensor, V: int, context: int, cap: int | None = None):
