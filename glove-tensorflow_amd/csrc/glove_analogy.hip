@@ -5,8 +5,8 @@
 //                            eval/python/evaluate.py, gensim most_similar).
 //
 // Four pieces on one stream: inverse row norms, the dense query rows, the n x V similarity GEMM (the kernel of the
-// PREDICT path with a dense query operand, the exclusion in its epilogue) and the staged top-k selection, the last
-// two shared with glove_predict.hip through glove_topk_kernels.h.
+// PREDICT path with a dense query operand, the exclusion in its epilogue) and the staged top-k selection, all but the
+// second shared with glove_predict.hip through glove_topk_kernels.h.
 #include "glove_common.h"
 #include "glove_topk_kernels.h"
 #include "../../include/glove_eval_hip.h"
@@ -14,8 +14,8 @@
 namespace glove {
 
 // Q[q] = w^_b - w^_a + w^_c and q_inv[q] = 1/sqrt(max(|Q[q]|^2, 1e-12)), one lane group per question.  The three
-// products and the sum of squares are spelled out as one fma chain per element and one butterfly per group: the
-// summation order is fixed, the result repeatable bit for bit whatever the grid.
+// products are spelled out as one fma chain per element, the sum of squares is row_sumsq's: the summation order is
+// fixed, the result repeatable bit for bit whatever the grid.
 template <int LPR, int NV>
 __global__ __launch_bounds__(kBlock) void analogy_query_kernel(const float *__restrict__ W, int d4,
                                                                const int32_t *__restrict__ abc, int32_t n,
@@ -27,25 +27,20 @@ __global__ __launch_bounds__(kBlock) void analogy_query_kernel(const float *__re
     for (int q = blockIdx.x * GPB + grp; q < n; q += gridDim.x * GPB) {
         const int32_t ia = abc[(size_t)q * 3], ib = abc[(size_t)q * 3 + 1], ic = abc[(size_t)q * 3 + 2];
         const float na = inv_norm[ia], nb = inv_norm[ib], nc = inv_norm[ic];
-        f4 a[NV], b[NV], c[NV];
+        f4 a[NV], b[NV], c[NV], x[NV];
         load_row_p<LPR, NV>(a, W, ia, d4, lg);
         load_row_p<LPR, NV>(b, W, ib, d4, lg);
         load_row_p<LPR, NV>(c, W, ic, d4, lg);
-        f4 *out = reinterpret_cast<f4 *>(Q) + (size_t)q * d4;
-        float s = 0.f;
 #pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            f4 x;
-            x.x = __builtin_fmaf(c[k].x, nc, __builtin_fmaf(-a[k].x, na, b[k].x * nb));
-            x.y = __builtin_fmaf(c[k].y, nc, __builtin_fmaf(-a[k].y, na, b[k].y * nb));
-            x.z = __builtin_fmaf(c[k].z, nc, __builtin_fmaf(-a[k].z, na, b[k].z * nb));
-            x.w = __builtin_fmaf(c[k].w, nc, __builtin_fmaf(-a[k].w, na, b[k].w * nb));
-            s += dot4(x, x);
-            const int i4 = lg + k * LPR;
-            if (i4 < d4) out[i4] = x;               // (lanes beyond the row hold zeros and store nothing)
+        for (int k = 0; k < NV; ++k) {                  // (lanes beyond the row hold zeros)
+            x[k].x = __builtin_fmaf(c[k].x, nc, __builtin_fmaf(-a[k].x, na, b[k].x * nb));
+            x[k].y = __builtin_fmaf(c[k].y, nc, __builtin_fmaf(-a[k].y, na, b[k].y * nb));
+            x[k].z = __builtin_fmaf(c[k].z, nc, __builtin_fmaf(-a[k].z, na, b[k].z * nb));
+            x[k].w = __builtin_fmaf(c[k].w, nc, __builtin_fmaf(-a[k].w, na, b[k].w * nb));
         }
-        s = group_sum<LPR>(s);
-        if (lg == 0) q_inv[q] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
+        store_row_p<LPR, NV>(Q, q, d4, lg, x);
+        const float s = row_sumsq<LPR, NV>(x);
+        if (lg == 0) q_inv[q] = clamped_inv_norm(s);
     }
 }
 
@@ -58,32 +53,21 @@ struct AnalogyWs {
 
 static AnalogyWs carve_analogy_ws(void *ws, int32_t n, int32_t V, int32_t d, int32_t k)
 {
+    WsCarver c{(char *)ws};
     AnalogyWs s;
-    size_t off = 0;
-    auto take = [&](size_t nfloats) {
-        float *p = (float *)((char *)ws + off);
-        off += align_up(nfloats * sizeof(float), 256);
-        return p;
-    };
-    s.inv_norm = take((size_t)V);
-    s.Q = take((size_t)n * d);
-    s.q_inv = take((size_t)n);
-    s.sims = take((size_t)n * V);
-    s.pingpong = (char *)ws + off;
-    s.bytes = off + topk_pingpong_bytes(n, V, k);
+    s.inv_norm = c.take<float>((size_t)V);
+    s.Q = c.take<float>((size_t)n * d);
+    s.q_inv = c.take<float>((size_t)n);
+    s.sims = c.take<float>((size_t)n * V);
+    s.pingpong = c.take<char>(topk_pingpong_bytes(n, V, k));
+    s.bytes = c.off;
     return s;
 }
 
-// What both entry points refuse.  k <= V - 3: a question excludes at most three ids, so at least k candidates carry a
-// finite score.  The selection (topk_select_kernel) orders a -inf score with a valid id behind every finite score and
-// ahead of its empty slots only (id 0x7fffffff, what `none` tests): an excluded id can be handed from one stage to
-// the next by a segment with fewer than k finite candidates, but the last stage sees all V - 3 >= k finite ones first
-// and never writes it.
+// What both entry points refuse (k <= V - 3: topk_k_ok says why)
 static bool analogy_sizes_ok(int32_t n, int32_t V, int32_t d, int32_t k)
 {
-    if (n < 0 || n > 65535 * kSimTile || V <= 0 || d <= 0 || (d % 4) != 0) return false;
-    if (k < 1 || k > 1024 || (int64_t)k > (int64_t)V - 3) return false;
-    return pick_row_shape(d / 4).lpr != 0;
+    return n >= 0 && n <= 65535 * kSimTile && sim_table_ok(V, d) && topk_k_ok(k, V, 3);
 }
 
 }  // namespace glove

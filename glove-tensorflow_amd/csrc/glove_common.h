@@ -35,6 +35,19 @@ __device__ inline void stamp(int slot)
 
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// Hands out the pieces of a workspace one behind the other, each 256-B aligned; `off` ends as the bytes they take.
+// (A null base only measures: nothing is dereferenced.)
+struct WsCarver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t count)
+    {
+        T *p = (T *)(base + off);
+        off += align_up(count * sizeof(T), 256);
+        return p;
+    }
+};
+
 // Small device buffers are zeroed by a KERNEL, never by hipMemsetAsync: captured into a hipGraph, a memset node of a few
 // words came back wrong on replay (ROCm 7.2: counts[4..7] of a plan held host-pointer-like garbage after the second
 // replay, tools/dbg_dyn_graph.py) — the cause of the GPU memory faults of the replayed dynamic index build.

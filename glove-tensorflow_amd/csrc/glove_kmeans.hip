@@ -1,13 +1,12 @@
 // Spherical k-means over the rows of an embedding table on gfx950: the third object of libglove_eval_hip.so,
 // include/glove_eval_cluster_hip.h (the semantics and the summation order are stated there).
 //
-//   glove_kmeans_assign_f32   every point's closest centroid by cosine: the similarity GEMM of glove_topk_kernels.h with
+//   glove_kmeans_assign_f32   every point's closest centroid by cosine: the similarity GEMM (glove_sim_gemm.h) with
 //                             the arg-max kept inside it — no n x K score matrix exists.
 //   glove_kmeans_update_f32   the new centroids, bitwise repeatable and without float atomics: a stable counting sort of
 //                             the point indices by cluster, then chunked segmented sums in a fixed order.
 //
-// inv_norm_kernel, the row helpers and the order topk_before come from glove_topk_kernels.h / glove_common.h, which
-// this file leaves as they are.
+// The inverse-norm kernels, the row helpers and the order topk_before come from glove_topk_kernels.h / glove_common.h.
 #include "glove_common.h"
 #include "glove_topk_kernels.h"
 #include "../../include/glove_eval_cluster_hip.h"
@@ -20,33 +19,13 @@ constexpr int kKmTile = 2048;                      // points per tile of the cou
 constexpr int kKmChunk = 64;                       // rows one lane group sums (the header states it: part of the bits)
 constexpr int kKmLevels = 4;                       // 64^4 > 65535 * 128: four summation levels reduce any cluster to one row
 
-// pinv[i] = 1 / sqrt(max(|W[ids[i]]|^2, 1e-12)): inv_norm_kernel's arithmetic on gathered rows (the same bits for the same row)
-template <int LPR, int NV>
-__global__ __launch_bounds__(kBlock) void point_inv_norm_kernel(const float *__restrict__ W, int d4,
-                                                                const int32_t *__restrict__ ids, int32_t n,
-                                                                float *__restrict__ pinv)
-{
-    constexpr int GPB = kBlock / LPR;
-    const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    for (int i = blockIdx.x * GPB + grp; i < n; i += gridDim.x * GPB) {
-        f4 r[NV];
-        load_row_p<LPR, NV>(r, W, ids[i], d4, lg);
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) s += dot4(r[k], r[k]);
-        s = group_sum<LPR>(s);
-        if (lg == 0) pinv[i] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-    }
-}
-
 // assign[i] = argmax_c (W[ids[i]] . C[c]) pinv[i] cinv[c] in the order topk_before, cos[i] the winner's score clamped.
-// Workgroup = 128 points; it walks the centroids in tiles of 128 and runs, per tile, the GEMM of cosine_mfma_kernel
-// (four waves of 2 x 2 blocks on v_mfma_f32_32x32x2_f32, operands through LDS in slabs of 32 columns, row stride 33
-// floats, the next slab's global loads in flight during the MFMAs) with the CENTROIDS on the A side: in the C/D map a
-// lane then holds 16 centroid rows (per block) of ONE point column, so the running arg-max of a point stays in two
-// registers of its lane.  At the end the two half-waves of a point's column exchange once, and the two waves that
-// hold the two centroid halves of a tile meet through LDS.  A dot product is a k-ordered fma chain: its bits do not
-// depend on the tile, the point's place in the call or n.
+// Workgroup = 128 points; it walks the centroids in tiles of 128 and runs, per tile, sim_tile_gemm (four waves of
+// 2 x 2 blocks, as in cosine_mfma_kernel) with the CENTROIDS on the A side: in the C/D map a lane then holds 16
+// centroid rows (per block) of ONE point column, so the running arg-max of a point stays in two registers of its
+// lane.  At the end the two half-waves of a point's column exchange once, and the two waves that hold the two
+// centroid halves of a tile meet through LDS.  A dot product is a k-ordered fma chain: its bits do not depend on the
+// tile, the point's place in the call or n.
 __global__ __launch_bounds__(kBlock) void kmeans_assign_kernel(const float *__restrict__ W, int32_t d,
                                                                const int32_t *__restrict__ ids, int32_t n,
                                                                const float *__restrict__ C, int32_t K,
@@ -71,57 +50,17 @@ __global__ __launch_bounds__(kBlock) void kmeans_assign_kernel(const float *__re
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;               // this wave's 64 centroids of a tile and 64 points
-    const int r32 = lane & 31, kh = lane >> 5;             // operand maps: A[i = lane & 31][k = lane >> 5], B likewise
+    const int r32 = lane & 31, kh = lane >> 5;
     float best[2] = {-INFINITY, -INFINITY};                // of point wn * 64 + b * 32 + r32, over this lane's centroid rows
     int32_t best_c[2] = {0x7fffffff, 0x7fffffff};
 
-    constexpr int kPer = kKmPoints * (kSimK / 4) / kBlock; // float4 per thread, operand and slab
-    f4 cn[kPer], pn[kPer];
     for (int c0 = 0; c0 < K; c0 += kKmCents) {
         __syncthreads();                                   // the last tile's epilogue has read c_inv
         if (threadIdx.x < kKmCents) c_inv[threadIdx.x] = c0 + threadIdx.x < K ? cinv[c0 + threadIdx.x] : 0.f;
         f32x16 acc[2][2];
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-        auto fetch = [&](int k0) {
-#pragma unroll
-            for (int x = 0; x < kPer; ++x) {
-                const int i = threadIdx.x + x * kBlock;
-                const int row = i / (kSimK / 4), c = (i % (kSimK / 4)) * 4;
-                const bool kin = k0 + c < d;               // d is a multiple of 4
-                const int32_t id = p_id[row];
-                cn[x] = pn[x] = f4{0.f, 0.f, 0.f, 0.f};
-                if (kin && c0 + row < K) cn[x] = *reinterpret_cast<const f4 *>(C + (size_t)(c0 + row) * d + k0 + c);
-                if (kin && id >= 0) pn[x] = *reinterpret_cast<const f4 *>(W + (size_t)id * d + k0 + c);
-            }
-        };
-        fetch(0);
-        for (int k0 = 0; k0 < d; k0 += kSimK) {
-#pragma unroll
-            for (int x = 0; x < kPer; ++x) {
-                const int i = threadIdx.x + x * kBlock;
-                const int row = i / (kSimK / 4), c = (i % (kSimK / 4)) * 4;
-                Cs[row][c] = cn[x].x; Cs[row][c + 1] = cn[x].y; Cs[row][c + 2] = cn[x].z; Cs[row][c + 3] = cn[x].w;
-                Ps[row][c] = pn[x].x; Ps[row][c + 1] = pn[x].y; Ps[row][c + 2] = pn[x].z; Ps[row][c + 3] = pn[x].w;
-            }
-            __syncthreads();
-            if (k0 + kSimK < d) fetch(k0 + kSimK);
-#pragma unroll 4
-            for (int kk = 0; kk < kSimK; kk += 2) {
-                const float a0 = Cs[wm * 64 + r32][kk + kh], a1 = Cs[wm * 64 + 32 + r32][kk + kh];
-                const float b0 = Ps[wn * 64 + r32][kk + kh], b1 = Ps[wn * 64 + 32 + r32][kk + kh];
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-        // C/D map: column (point) = lane & 31, row (centroid) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+        sim_tile_gemm(Cs, Ps, acc, C, W, d, [&](int row) { return c0 + row < K ? c0 + row : -1; },
+                      [&](int row) { return p_id[row]; }, wm * 64, 32, wn * 64);
+        // C/D map: column = point, row = centroid
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
             const float pi = p_inv[wn * 64 + b * 32 + r32];
@@ -129,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void kmeans_assign_kernel(const float *__re
             for (int a = 0; a < 2; ++a) {
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
-                    const int cl = wm * 64 + a * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh, c = c0 + cl;
+                    const int cl = wm * 64 + a * 32 + sim_cd_row(reg, kh), c = c0 + cl;
                     const float s = acc[a][b][reg] * pi * c_inv[cl];
                     if (c < K && topk_before(s, c, best[b], best_c[b])) { best[b] = s; best_c[b] = c; }
                 }
@@ -155,7 +94,7 @@ __global__ __launch_bounds__(kBlock) void kmeans_assign_kernel(const float *__re
             if (p0 + pl < n) {
                 const bool none = best_c[b] == 0x7fffffff;      // every score a NaN: the point goes to cluster 0
                 assign_out[p0 + pl] = none ? 0 : best_c[b];
-                cos_out[p0 + pl] = none ? 0.f : fminf(fmaxf(best[b], -1.0f), 1.0f);
+                cos_out[p0 + pl] = none ? 0.f : clamp_cos(best[b]);
             }
         }
     }
@@ -303,11 +242,7 @@ __global__ __launch_bounds__(kBlock) void kmeans_segsum_kernel(const float *__re
             f4 r[NV];
             if constexpr (FIRST) {
                 load_row_p<LPR, NV>(r, W, ids[sorted[first + t]], d4, lg);
-                float s = 0.f;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) s += dot4(r[k], r[k]);
-                s = group_sum<LPR>(s);
-                const float inv = 1.0f / sqrtf(fmaxf(s, 1e-12f));
+                const float inv = clamped_inv_norm(row_sumsq<LPR, NV>(r));
 #pragma unroll
                 for (int k = 0; k < NV; ++k) r[k] *= inv;
             } else {
@@ -316,12 +251,7 @@ __global__ __launch_bounds__(kBlock) void kmeans_segsum_kernel(const float *__re
 #pragma unroll
             for (int k = 0; k < NV; ++k) acc[k] = t == 0 ? r[k] : acc[k] + r[k];
         }
-        f4 *o = reinterpret_cast<f4 *>(dst) + (size_t)g * d4;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i4 = lg + k * LPR;
-            if (i4 < d4) o[i4] = acc[k];
-        }
+        store_row_p<LPR, NV>(dst, g, d4, lg, acc);
     }
 }
 
@@ -340,17 +270,12 @@ __global__ __launch_bounds__(kBlock) void kmeans_finish_kernel(const float *__re
         const bool empty = counts[c] == 0;
         if (empty) load_row_p<LPR, NV>(r, C_in, c, d4, lg);
         else load_row_p<LPR, NV>(r, sums, st_last[c], d4, lg);
-        float s = 0.f;
+        const float inv = clamped_inv_norm(row_sumsq<LPR, NV>(r));
+        if (!empty) {
 #pragma unroll
-        for (int k = 0; k < NV; ++k) s += dot4(r[k], r[k]);
-        s = group_sum<LPR>(s);
-        const float inv = empty ? 1.0f : 1.0f / sqrtf(fmaxf(s, 1e-12f));
-        f4 *o = reinterpret_cast<f4 *>(C_out) + (size_t)c * d4;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            const int i4 = lg + k * LPR;
-            if (i4 < d4) o[i4] = empty ? r[k] : r[k] * inv;
+            for (int k = 0; k < NV; ++k) r[k] *= inv;
         }
+        store_row_p<LPR, NV>(C_out, c, d4, lg, r);
     }
 }
 
@@ -366,31 +291,25 @@ struct KmeansWs {
 
 static KmeansWs carve_kmeans_ws(void *ws, int32_t n, int32_t d, int32_t K)
 {
+    WsCarver c{(char *)ws};
     KmeansWs s;
-    size_t off = 0;
-    auto take = [&](size_t words) {
-        void *p = (char *)ws + off;
-        off += align_up(words * 4, 256);
-        return p;
-    };
     s.ntiles = (n + kKmTile - 1) / kKmTile;
     s.rows[0] = (int64_t)n / kKmChunk + K;
     s.rows[1] = s.rows[0] / kKmChunk + K;
-    s.pinv = (float *)take((size_t)n);
-    s.cinv = (float *)take((size_t)K);
-    s.hist = (int32_t *)take((size_t)s.ntiles * K);
-    s.starts = (int32_t *)take((size_t)(kKmLevels + 1) * (K + 1));
-    s.sorted = (int32_t *)take((size_t)n);
-    s.sums[0] = (float *)take((size_t)s.rows[0] * d);
-    s.sums[1] = (float *)take((size_t)s.rows[1] * d);
-    s.bytes = off;
+    s.pinv = c.take<float>((size_t)n);
+    s.cinv = c.take<float>((size_t)K);
+    s.hist = c.take<int32_t>((size_t)s.ntiles * K);
+    s.starts = c.take<int32_t>((size_t)(kKmLevels + 1) * (K + 1));
+    s.sorted = c.take<int32_t>((size_t)n);
+    s.sums[0] = c.take<float>((size_t)s.rows[0] * d);
+    s.sums[1] = c.take<float>((size_t)s.rows[1] * d);
+    s.bytes = c.off;
     return s;
 }
 
 static bool kmeans_sizes_ok(int32_t n, int32_t V, int32_t d, int32_t K)
 {
-    if (n < 0 || n > 65535 * 128 || V <= 0 || K < 1 || K > kKmMaxK) return false;
-    return d > 0 && (d % 4) == 0 && pick_row_shape(d / 4).lpr != 0;
+    return n >= 0 && n <= 65535 * 128 && K >= 1 && K <= kKmMaxK && sim_table_ok(V, d);
 }
 
 }  // namespace glove
@@ -420,7 +339,7 @@ int glove_kmeans_assign_f32(const float *W, int32_t V, int32_t d, const int32_t 
     const int nbp = blocks_for(n, kBlock / shape.lpr), nbc = blocks_for(K, kBlock / shape.lpr);
     hipStream_t st = (hipStream_t)stream;
 #define CALL(LPR, NV)                                                                                                  \
-    hipLaunchKernelGGL((point_inv_norm_kernel<LPR, NV>), dim3(nbp), dim3(kBlock), 0, st, W, d4, ids, n, w.pinv);       \
+    hipLaunchKernelGGL((gathered_inv_norm_kernel<LPR, NV>), dim3(nbp), dim3(kBlock), 0, st, W, d4, ids, n, w.pinv);    \
     hipLaunchKernelGGL((inv_norm_kernel<LPR, NV>), dim3(nbc), dim3(kBlock), 0, st, C, K, d4, w.cinv)
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL

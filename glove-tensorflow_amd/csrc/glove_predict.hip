@@ -5,7 +5,9 @@
 //                          eval pass) — forward only, tables untouched.
 //   glove_topk_cosine_f32  get_predictions (src/models/model_utils.py:81-110): cosine_similarity
 //                          (src/models/utils.py:12-19) of query ROW embeddings against all V row
-//                          embeddings + tf.math.top_k (descending, ties -> lower index).
+//                          embeddings + tf.math.top_k (descending, ties -> lower index).  Its kernels
+//                          are those of glove_topk_kernels.h, shared with libglove_eval_hip.so; the GEMM's
+//                          tile loop is glove_sim_gemm.h.
 #include "glove_common.h"
 #include "glove_topk_kernels.h"
 
@@ -58,6 +60,24 @@ __global__ __launch_bounds__(kBlock) void eval_kernel(const int32_t *__restrict_
     }
 }
 
+// the workspace: inv_norm[V] | sims[n V] | two ping-pong buffers of winners, each piece 256-B aligned
+struct TopkWs {
+    float *inv_norm, *sims;
+    void *pingpong;
+    size_t bytes;
+};
+
+static TopkWs carve_topk_ws(void *ws, int32_t n, int32_t V, int32_t k)
+{
+    WsCarver c{(char *)ws};
+    TopkWs s;
+    s.inv_norm = c.take<float>((size_t)V);
+    s.sims = c.take<float>((size_t)n * V);
+    s.pingpong = c.take<char>(topk_pingpong_bytes(n, V, k));
+    s.bytes = c.off;
+    return s;
+}
+
 }  // namespace glove
 
 using namespace glove;
@@ -101,30 +121,29 @@ static int launch_eval(const int32_t *row, const int32_t *col, const float *w, c
 size_t glove_topk_workspace_bytes(int32_t n, int32_t V, int32_t k)
 {
     if (n < 0 || V <= 0 || k < 0) return 0;
-    return align_up((size_t)V * sizeof(float), 256) + align_up((size_t)n * V * sizeof(float), 256) +
-           topk_pingpong_bytes(n, V, k);                                        // two ping-pong buffers of winners
+    return carve_topk_ws(nullptr, n, V, k).bytes;
 }
 
 int glove_topk_cosine_f32(const float *R, int32_t V, int32_t d, const int32_t *query_ids, int32_t n, int32_t k,
                           float *sims_out, int32_t *idx_out, void *ws, size_t ws_bytes, void *stream)
 {
-    if (!R || V <= 0 || d <= 0 || (d % 4) != 0 || n < 0 || n > 65535 * kSimTile || k <= 0 || k > V || k > 1024) return GLOVE_E_BADARG;
+    // (not sim_table_ok: a d beyond the widest row shape is refused behind the workspace check, as it always was)
+    if (!R || V <= 0 || d <= 0 || (d % 4) != 0 || n < 0 || n > 65535 * kSimTile || !topk_k_ok(k, V, 0)) return GLOVE_E_BADARG;
     if (n == 0) return 0;
     if (!query_ids || !sims_out || !idx_out || !ws) return GLOVE_E_BADARG;
-    if (glove_topk_workspace_bytes(n, V, k) > ws_bytes) return GLOVE_E_WORKSPACE;
-    float *inv_norm = (float *)ws;
-    float *sims = (float *)((char *)ws + align_up((size_t)V * sizeof(float), 256));
+    const TopkWs w = carve_topk_ws(ws, n, V, k);
+    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
     const int d4 = d / 4;
     const RowShape shape = pick_row_shape(d4);
     if (shape.lpr == 0) return GLOVE_E_BADARG;
     const int nbv = blocks_for(V, kBlock / shape.lpr);
     hipStream_t st = (hipStream_t)stream;
-#define CALL(LPR, NV) hipLaunchKernelGGL((inv_norm_kernel<LPR, NV>), dim3(nbv), dim3(kBlock), 0, st, R, V, d4, inv_norm)
+#define CALL(LPR, NV) hipLaunchKernelGGL((inv_norm_kernel<LPR, NV>), dim3(nbv), dim3(kBlock), 0, st, R, V, d4, w.inv_norm)
     GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
     hipLaunchKernelGGL(cosine_mfma_kernel<GatheredQueries>, dim3((V + kSimTile - 1) / kSimTile, (n + kSimTile - 1) / kSimTile),
-                       dim3(kBlock), 0, st, R, V, d, GatheredQueries{query_ids}, n, inv_norm, sims);
-    launch_topk_stages(sims, n, V, k, sims_out, idx_out, (char *)sims + align_up((size_t)n * V * sizeof(float), 256), st);
+                       dim3(kBlock), 0, st, R, V, d, GatheredQueries{query_ids}, n, w.inv_norm, w.sims);
+    launch_topk_stages(w.sims, n, V, k, sims_out, idx_out, w.pingpong, st);
     return (int)hipGetLastError();
 }
 

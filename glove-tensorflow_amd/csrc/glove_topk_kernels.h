@@ -1,13 +1,17 @@
-// Kernels that two libraries share: the cosine top-k of the PREDICT path (glove_predict.hip, libglove_hip.so) and the
-// word-analogy top-k (glove_analogy.hip, libglove_eval_hip.so).  Each library compiles its own copy: kernels are shared,
-// state is not (there is none).
+// Kernels and host helpers that libglove_hip.so (the PREDICT path, glove_predict.hip) and libglove_eval_hip.so
+// (glove_analogy.hip, glove_cosmul.hip, glove_kmeans.hip) share.  Each library compiles its own copy: kernels are
+// shared, state is not (there is none).
 //
-//   inv_norm_kernel      1 / |R_v| per row (tf.math.l2_normalize's clamp)
-//   cosine_mfma_kernel   the n x V similarity GEMM on the matrix cores, over where the query operand comes from
+//   load_row_p / store_row_p / row_sumsq / clamped_inv_norm / clamp_cos   a lane group's view of one row
+//   inv_norm_kernel / gathered_inv_norm_kernel   1 / |R_v| per row (tf.math.l2_normalize's clamp)
+//   cosine_mfma_kernel   the n x V similarity GEMM on the matrix cores (the tile loop: glove_sim_gemm.h), over where the
+//                        query operand comes from
 //   topk_select_kernel   staged top-k selection in the order of tf.math.top_k
 //   launch_topk_stages   the host loop that runs the selection until one segment is left
+//   sim_table_ok / topk_k_ok   the size checks of the entry points
 #pragma once
 #include "glove_common.h"
+#include "glove_sim_gemm.h"
 
 namespace glove {
 
@@ -22,22 +26,60 @@ __device__ inline void load_row_p(f4 (&dst)[NV], const float *table, int32_t id,
     }
 }
 
-// inv_norm[v] = 1/sqrt(max(|R_v|^2, 1e-12))  (tf.math.l2_normalize epsilon)
+// ... and its mirror (lanes beyond the row store nothing)
+template <int LPR, int NV>
+__device__ inline void store_row_p(float *table, int64_t id, int d4, int lg, const f4 (&src)[NV])
+{
+    f4 *p = reinterpret_cast<f4 *>(table) + (size_t)id * d4;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const int i4 = lg + k * LPR;
+        if (i4 < d4) p[i4] = src[k];
+    }
+}
+
+// |r|^2 of the row a lane group holds: one fma chain per lane, one butterfly per group — a fixed summation order
+template <int LPR, int NV>
+__device__ inline float row_sumsq(const f4 (&r)[NV])
+{
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s += dot4(r[k], r[k]);
+    return group_sum<LPR>(s);
+}
+
+// 1/sqrt(max(|r|^2, 1e-12))  (tf.math.l2_normalize epsilon)
+__device__ inline float clamped_inv_norm(float sumsq) { return 1.0f / sqrtf(fmaxf(sumsq, 1e-12f)); }
+
+__device__ inline float clamp_cos(float c) { return fminf(fmaxf(c, -1.0f), 1.0f); }
+
+// out[v] = clamped_inv_norm of row ids[v] of R (row v itself where ids is null), v < n: one lane group per row
+template <int LPR, int NV>
+__device__ inline void inv_norm_rows(const float *R, const int32_t *ids, int32_t n, int d4, float *out)
+{
+    constexpr int GPB = kBlock / LPR;
+    const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
+    for (int v = blockIdx.x * GPB + grp; v < n; v += gridDim.x * GPB) {
+        f4 r[NV];
+        load_row_p<LPR, NV>(r, R, ids ? ids[v] : v, d4, lg);
+        const float s = row_sumsq<LPR, NV>(r);
+        if (lg == 0) out[v] = clamped_inv_norm(s);
+    }
+}
+
 template <int LPR, int NV>
 __global__ __launch_bounds__(kBlock) void inv_norm_kernel(const float *__restrict__ R, int32_t V, int d4,
                                                           float *__restrict__ inv_norm)
 {
-    constexpr int GPB = kBlock / LPR;
-    const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
-    for (int v = blockIdx.x * GPB + grp; v < V; v += gridDim.x * GPB) {
-        f4 r[NV];
-        load_row_p<LPR, NV>(r, R, v, d4, lg);
-        float s = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) s += dot4(r[k], r[k]);
-        s = group_sum<LPR>(s);
-        if (lg == 0) inv_norm[v] = 1.0f / sqrtf(fmaxf(s, 1e-12f));
-    }
+    inv_norm_rows<LPR, NV>(R, nullptr, V, d4, inv_norm);
+}
+
+template <int LPR, int NV>
+__global__ __launch_bounds__(kBlock) void gathered_inv_norm_kernel(const float *__restrict__ W, int d4,
+                                                                   const int32_t *__restrict__ ids, int32_t n,
+                                                                   float *__restrict__ pinv)
+{
+    inv_norm_rows<LPR, NV>(W, ids, n, d4, pinv);
 }
 
 // Where the query operand of the similarity GEMM comes from.
@@ -56,13 +98,10 @@ struct DenseQueries {
 };
 
 // sims[q, v] = (query_q . R[v]) q_inv[q] inv_norm[v]: the one GEMM-shaped piece of the path
-// (tf.matmul of the l2-normalised query rows with all rows, utils.py:12-19), on the matrix cores in exact f32:
-// v_mfma_f32_32x32x2_f32 is a k-ordered fmaf chain, so the numerics are those of a scalar loop.
-// Workgroup = 128 queries x 128 vocabulary rows, four waves of 2 x 2 MFMA tiles (64 accumulator VGPRs); the
-// operands go through LDS in slabs of 32 columns (row stride 33 floats: a tile column is read conflict-free).
-// One call reads R once per 128 queries instead of once per 4.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int kSimTile = 128, kSimK = 32;
+// (tf.matmul of the l2-normalised query rows with all rows, utils.py:12-19), on the matrix cores in exact f32.
+// Workgroup = 128 queries x 128 vocabulary rows, four waves of 2 x 2 MFMA blocks (64 accumulator VGPRs) through
+// sim_tile_gemm.  One call reads R once per 128 queries instead of once per 4.
+constexpr int kSimTile = 128;
 
 template <class Src>
 __global__ __launch_bounds__(kBlock) void cosine_mfma_kernel(const float *__restrict__ R, int32_t V, int32_t d,
@@ -87,57 +126,17 @@ __global__ __launch_bounds__(kBlock) void cosine_mfma_kernel(const float *__rest
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm = wave >> 1, wn = wave & 1;               // this wave's 64 x 64 quadrant of the tile
-    const int r32 = lane & 31, kh = lane >> 5;             // operand maps: A[i = lane & 31][k = lane >> 5], B likewise
+    const int r32 = lane & 31, kh = lane >> 5;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-
-    // a slab = 128 rows x 32 columns of each operand: 8 threads x 16 B per row, zero beyond n / V / d.  The next
-    // slab's global loads are issued before the MFMAs of the current one and land in LDS after them.
-    constexpr int kPer = kSimTile * (kSimK / 4) / kBlock;  // float4 per thread, operand and slab
-    f4 qn[kPer], rn[kPer];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int x = 0; x < kPer; ++x) {
-            const int i = threadIdx.x + x * kBlock;
-            const int row = i / (kSimK / 4), c = (i % (kSimK / 4)) * 4;
-            const bool kin = k0 + c < d;                   // d is a multiple of 4
-            qn[x] = rn[x] = f4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (Src::kDense) {
-                if (kin && q0 + row < n) qn[x] = *reinterpret_cast<const f4 *>(src.Q + (size_t)(q0 + row) * d + k0 + c);
-            } else {
-                if (kin && q0 + row < n) qn[x] = *reinterpret_cast<const f4 *>(R + (size_t)src.qid[q0 + row] * d + k0 + c);
-            }
-            if (kin && v0 + row < V) rn[x] = *reinterpret_cast<const f4 *>(R + (size_t)(v0 + row) * d + k0 + c);
-        }
+    const auto q_id = [&](int row) -> int32_t {
+        if (q0 + row >= n) return -1;
+        if constexpr (Src::kDense) return q0 + row;
+        else return src.qid[q0 + row];
     };
-    fetch(0);
-    for (int k0 = 0; k0 < d; k0 += kSimK) {
-#pragma unroll
-        for (int x = 0; x < kPer; ++x) {
-            const int i = threadIdx.x + x * kBlock;
-            const int row = i / (kSimK / 4), c = (i % (kSimK / 4)) * 4;
-            Qs[row][c] = qn[x].x; Qs[row][c + 1] = qn[x].y; Qs[row][c + 2] = qn[x].z; Qs[row][c + 3] = qn[x].w;
-            Rs[row][c] = rn[x].x; Rs[row][c + 1] = rn[x].y; Rs[row][c + 2] = rn[x].z; Rs[row][c + 3] = rn[x].w;
-        }
-        __syncthreads();
-        if (k0 + kSimK < d) fetch(k0 + kSimK);
-#pragma unroll 4
-        for (int kk = 0; kk < kSimK; kk += 2) {
-            const float a0 = Qs[wm * 64 + r32][kk + kh], a1 = Qs[wm * 64 + 32 + r32][kk + kh];
-            const float b0 = Rs[wn * 64 + r32][kk + kh], b1 = Rs[wn * 64 + 32 + r32][kk + kh];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        __syncthreads();
-    }
-    // C/D map: column (vocabulary row) = lane & 31, row (query) = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const float *Q = R;
+    if constexpr (Src::kDense) Q = src.Q;
+    sim_tile_gemm(Qs, Rs, acc, Q, R, d, q_id, [&](int row) { return v0 + row < V ? v0 + row : -1; }, wm * 64, 32, wn * 64);
+    // C/D map: column = vocabulary row, row = query
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
         const int v = v0 + wn * 64 + b * 32 + r32;
@@ -146,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void cosine_mfma_kernel(const float *__rest
         for (int a = 0; a < 2; ++a) {
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
-                const int ql = wm * 64 + a * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kh, q = q0 + ql;
+                const int ql = wm * 64 + a * 32 + sim_cd_row(reg, kh), q = q0 + ql;
                 if constexpr (Src::kDense) {
                     // the exclusion rides in the one store of (q, v): no second writer to sims, no ordering question
                     const bool own = v == q_excl[ql][0] || v == q_excl[ql][1] || v == q_excl[ql][2];
@@ -157,6 +156,19 @@ __global__ __launch_bounds__(kBlock) void cosine_mfma_kernel(const float *__rest
             }
         }
     }
+}
+
+// What the entry points take for a table: rows of d floats, d a multiple of 4 that some row shape covers
+inline bool sim_table_ok(int32_t V, int32_t d) { return V > 0 && d > 0 && (d % 4) == 0 && pick_row_shape(d / 4).lpr != 0; }
+
+// ... and for k, where a query never returns `excluded` ids of its own (3 for an analogy question, 0 for PREDICT):
+// k <= V - excluded, so at least k candidates carry a finite score.  The selection (topk_select_kernel) orders a -inf
+// score with a valid id behind every finite score and ahead of its empty slots only (id 0x7fffffff, what `none`
+// tests): an excluded id can be handed from one stage to the next by a segment with fewer than k finite candidates,
+// but the last stage sees all V - excluded >= k finite ones first and never writes it.
+inline bool topk_k_ok(int32_t k, int32_t V, int32_t excluded)
+{
+    return k >= 1 && k <= 1024 && (int64_t)k <= (int64_t)V - excluded;
 }
 
 // order of tf.math.top_k: larger similarity first, ties -> lower index first

@@ -1323,11 +1323,9 @@ class GloveHip:
                                               _ptr(ws), ws.numel(), _stream()), "glove_topk_cosine_f32")
         return sims, idx
 
-    def analogy_topk(self, W: torch.Tensor, abc: torch.Tensor, k: int, batch: int = 1024):
-        """3CosAdd word analogies (include/glove_eval_hip.h): for the questions abc [n,3] = (a, b, c) the k rows of W [V,d]
-        closest by cosine to w^_b - w^_a + w^_c, a, b and c themselves left out -> (sims, idx) [n,k], descending, ties to
-        the lower id.  The scores of `batch` questions are a [batch, V] matrix in the workspace: the questions are walked
-        in batches of that size through one workspace.  The ids of abc must lie in [0, V): the kernels do not look."""
+    def _analogy_batches(self, W: torch.Tensor, abc: torch.Tensor, k: int, batch: int, sizes: str, entry: str, *extra):
+        """What analogy_topk and analogy_cosmul_topk share: the checks, the outputs, one workspace of `sizes`(batch
+        questions) bytes and the walk of the questions through `entry` in batches; `extra` goes between k and the outputs."""
         _require(W, torch.float32); _require(abc, torch.int32)
         if W.dim() != 2 or abc.dim() != 2 or abc.shape[1] != 3:
             raise GloveHipError("expected W [V,d] and abc [n,3]")
@@ -1338,34 +1336,26 @@ class GloveHip:
         n = int(abc.shape[0])
         sims = torch.empty(n, k, dtype=torch.float32, device=W.device)
         idx = torch.empty(n, k, dtype=torch.int32, device=W.device)
-        ws = torch.empty(max(lib.glove_analogy_workspace_bytes(min(batch, n), V, d, k), 256), dtype=torch.uint8, device=W.device)
+        ws = torch.empty(max(getattr(lib, sizes)(min(batch, n), V, d, k), 256), dtype=torch.uint8, device=W.device)
         for s in range(0, max(n, 1), batch):      # (n == 0: one call, which checks the sizes and launches nothing)
             m = min(batch, n - s)
-            _check(lib.glove_analogy_topk_f32(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, _ptr(sims[s:s + m]), _ptr(idx[s:s + m]),
-                                              _ptr(ws), ws.numel(), _stream()), "glove_analogy_topk_f32")
+            _check(getattr(lib, entry)(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, *extra, _ptr(sims[s:s + m]), _ptr(idx[s:s + m]),
+                                       _ptr(ws), ws.numel(), _stream()), entry)
         return sims, idx
+
+    def analogy_topk(self, W: torch.Tensor, abc: torch.Tensor, k: int, batch: int = 1024):
+        """3CosAdd word analogies (include/glove_eval_hip.h): for the questions abc [n,3] = (a, b, c) the k rows of W [V,d]
+        closest by cosine to w^_b - w^_a + w^_c, a, b and c themselves left out -> (sims, idx) [n,k], descending, ties to
+        the lower id.  The scores of `batch` questions are a [batch, V] matrix in the workspace: the questions are walked
+        in batches of that size through one workspace.  The ids of abc must lie in [0, V): the kernels do not look."""
+        return self._analogy_batches(W, abc, k, batch, "glove_analogy_workspace_bytes", "glove_analogy_topk_f32")
 
     def analogy_cosmul_topk(self, W: torch.Tensor, abc: torch.Tensor, k: int, eps: float = 1e-3, batch: int = 1024):
         """3CosMul word analogies (include/glove_eval_sim_hip.h): for the questions abc [n,3] = (a, b, c) the k rows v of
         W [V,d] with the largest s(b, v) s(c, v) / (s(a, v) + eps), s = (1 + cos) / 2, a, b and c themselves left out ->
         (scores, idx) [n,k], descending, ties to the lower id.  Walks the questions in batches through one workspace like
         analogy_topk; a question's scores do not depend on its batch.  The ids of abc must lie in [0, V)."""
-        _require(W, torch.float32); _require(abc, torch.int32)
-        if W.dim() != 2 or abc.dim() != 2 or abc.shape[1] != 3:
-            raise GloveHipError("expected W [V,d] and abc [n,3]")
-        if batch < 1:
-            raise GloveHipError("batch must be positive, got %d" % batch)
-        lib = load_eval_library()
-        V, d = W.shape
-        n = int(abc.shape[0])
-        sims = torch.empty(n, k, dtype=torch.float32, device=W.device)
-        idx = torch.empty(n, k, dtype=torch.int32, device=W.device)
-        ws = torch.empty(max(lib.glove_cosmul_workspace_bytes(min(batch, n), V, d, k), 256), dtype=torch.uint8, device=W.device)
-        for s in range(0, max(n, 1), batch):      # (n == 0: one call, which checks the sizes and launches nothing)
-            m = min(batch, n - s)
-            _check(lib.glove_cosmul_topk_f32(_ptr(W), V, d, _ptr(abc[s:s + m]), m, k, float(eps), _ptr(sims[s:s + m]),
-                                             _ptr(idx[s:s + m]), _ptr(ws), ws.numel(), _stream()), "glove_cosmul_topk_f32")
-        return sims, idx
+        return self._analogy_batches(W, abc, k, batch, "glove_cosmul_workspace_bytes", "glove_cosmul_topk_f32", float(eps))
 
     def pair_cosine(self, W: torch.Tensor, pairs: torch.Tensor) -> torch.Tensor:
         """The cosine of the rows pairs[i,0] and pairs[i,1] of W [V,d] -> [n] (include/glove_eval_sim_hip.h), the norms
