@@ -1,6 +1,6 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
 include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h), of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
-include/glove_text_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h).
+include/glove_text_hip.h, include/glove_vectors_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -37,6 +37,10 @@ COOC_MERGE_TILE = 2048              # GLOVE_COOC_MERGE_TILE: merged positions on
 GLOVE_TEXT_ABI_VERSION = 1          # include/glove_text_hip.h: the same library's second header (tokenizing), versioned on its own
 TEXT_TILE_BYTES = 4096              # GLOVE_TEXT_TILE_BYTES: bytes of a block one workgroup of glove_text_tokenize_u8 owns
 TEXT_MAX_TOKEN = 65535              # GLOVE_TEXT_MAX_TOKEN: bytes of a token its hash covers; the longest length a `where` word holds
+GLOVE_VECTORS_ABI_VERSION = 1       # include/glove_vectors_hip.h: the same library's third header (word-vector files), versioned on its own
+VECTORS_TILE_BYTES = 4096           # GLOVE_VECTORS_TILE_BYTES: bytes of a block one workgroup of glove_vectors_lines_u8 owns
+VECTORS_MAX_SPAN = 65535            # GLOVE_VECTORS_MAX_SPAN: the longest token length a fallback span holds
+VECTORS_MAX_D = 65536               # GLOVE_VECTORS_MAX_D: the most numbers per record / columns of a table
 GLOVE_FACTOR_ABI_VERSION = 1        # include/glove_factor_hip.h (libglove_factor_hip.so)
 FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one lane group of glove_csr_spmm_f32 sums
 REWEIGHT_KINDS = {"none": 0, "sqrt": 1, "log1p": 2, "ppmi": 3}      # GLOVE_REWEIGHT_*
@@ -97,6 +101,9 @@ PREP_EXPORTED_SYMBOLS = ("glove_cooc_stream_abi_version", "glove_cooc_chunk_work
 TEXT_EXPORTED_SYMBOLS = ("glove_text_abi_version", "glove_text_tokenize_workspace_bytes", "glove_text_tokenize_u8",
                          "glove_text_block_vocab_workspace_bytes", "glove_text_block_vocab",
                          "glove_text_vocab_merge_workspace_bytes", "glove_text_vocab_merge", "glove_text_token_ids_i32")
+# every symbol include/glove_vectors_hip.h declares (the same library)
+VECTORS_EXPORTED_SYMBOLS = ("glove_vectors_abi_version", "glove_vectors_lines_workspace_bytes", "glove_vectors_lines_u8",
+                            "glove_vectors_parse_f32", "glove_vectors_format_workspace_bytes", "glove_vectors_format_f32")
 # every symbol include/glove_factor_hip.h declares (libglove_factor_hip.so)
 FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace_bytes", "glove_csr_spmm_f32",
                            "glove_csr_row_sums_f64", "glove_coo_reweight_f32")
@@ -266,7 +273,7 @@ _prep_lib = None
 
 
 def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h) and declare the prototypes, at the first call that needs
+    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h, include/glove_vectors_hip.h) and declare the prototypes, at the first call that needs
     it: training never loads it.  Raises if it is not built, like load_library."""
     global _prep_lib
     if _prep_lib is not None and path is None:
@@ -288,6 +295,12 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_text_vocab_merge_workspace_bytes": (sz, [i64, i64]),
         "glove_text_vocab_merge": (C.c_int, [vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, sz, vp]),
         "glove_text_token_ids_i32": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp, vp, vp]),
+        "glove_vectors_abi_version": (C.c_int, []),
+        "glove_vectors_lines_workspace_bytes": (sz, [i64, i64]),
+        "glove_vectors_lines_u8": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_vectors_parse_f32": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+        "glove_vectors_format_workspace_bytes": (sz, [i64, i32]),
+        "glove_vectors_format_f32": (C.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
     }
     lib = _open(Path(path) if path else PREP_LIB_PATH, protos)
     if lib.glove_cooc_stream_abi_version() != GLOVE_COOC_STREAM_ABI_VERSION:
@@ -296,6 +309,9 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_text_abi_version() != GLOVE_TEXT_ABI_VERSION:
         raise GloveHipError("ABI mismatch: prep library (text entry points) %d, binding %d"
                             % (lib.glove_text_abi_version(), GLOVE_TEXT_ABI_VERSION))
+    if lib.glove_vectors_abi_version() != GLOVE_VECTORS_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: prep library (word-vector entry points) %d, binding %d"
+                            % (lib.glove_vectors_abi_version(), GLOVE_VECTORS_ABI_VERSION))
     if path is None:
         _prep_lib = lib
     return lib
@@ -1741,3 +1757,97 @@ class GloveHip:
         sizes = torch.tensor([int(hashes.numel()), 0, 0], dtype=torch.int64).to(hashes.device)
         self.text_token_ids_enqueue(block, start, length, hashes, sizes[0:1], kept, ids, sizes[1:3])
         return ids, int(sizes[1].item())
+
+    # ---- reading and writing word-vector text files (include/glove_vectors_hip.h): what trainer.vectors drives
+    def vectors_lines_enqueue(self, block, line_start, line_fields, n_lines, ws=None):
+        """glove_vectors_lines_u8 on the current stream, nothing read back: block uint8 [n_bytes]; line_start / line_fields
+        int32 [cap]; n_lines an int64 device tensor ([>= 2] where the block may be empty)."""
+        lib = load_prep_library()
+        cap = int(line_start.numel())
+        _require(block, torch.uint8); _require(line_start, torch.int32); _require(line_fields, torch.int32, cap)
+        _require(n_lines, torch.int64)
+        n_bytes = int(block.numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_vectors_lines_workspace_bytes(n_bytes, cap), "glove_vectors_lines_workspace_bytes")
+        _check(lib.glove_vectors_lines_u8(_ptr(block) if n_bytes else None, n_bytes, _ptr(line_start), _ptr(line_fields),
+                                          _ptr(n_lines), cap, _ptr(ws), ws.numel(), _stream()), "glove_vectors_lines_u8")
+
+    def vectors_parse_enqueue(self, block, line_start, n_lines, d: int, vec, word_len, fb_index, fb_span, n_fallback):
+        """glove_vectors_parse_f32 on the current stream, nothing read back: vec float32 [cap_lines, ld] (ld % 4 == 0), word_len
+        int32 [cap_lines], fb_index / fb_span int64 [cap_fb], n_lines int64 [>= 1], n_fallback int64 [>= 2]."""
+        lib = load_prep_library()
+        cap_lines, cap_fb = int(line_start.numel()), int(fb_index.numel())
+        _require(block, torch.uint8); _require(line_start, torch.int32); _require(word_len, torch.int32, cap_lines)
+        _require(vec, torch.float32); _require(fb_index, torch.int64); _require(fb_span, torch.int64, cap_fb)
+        _require(n_lines, torch.int64); _require(n_fallback, torch.int64)
+        if vec.dim() != 2 or vec.shape[0] != cap_lines:
+            raise GloveHipError("vec must be [%d, ld], got %s" % (cap_lines, tuple(vec.shape)))
+        _check(lib.glove_vectors_parse_f32(_ptr(block) if block.numel() else None, int(block.numel()), _ptr(line_start), _ptr(n_lines),
+                                           cap_lines, int(d), int(vec.shape[1]), _ptr(vec), _ptr(word_len),
+                                           _ptr(fb_index) if cap_fb else None, _ptr(fb_span) if cap_fb else None, _ptr(n_fallback),
+                                           cap_fb, _stream()), "glove_vectors_parse_f32")
+
+    def vectors_format_enqueue(self, W, d: int, precision: int, word_bytes, word_off, out, row_off, host_row, n_host_rows, ws=None):
+        """glove_vectors_format_f32 on the current stream, nothing read back: W float32 [n_rows, ld]; word_bytes uint8, word_off
+        int64 [n_rows + 1]; out uint8 [cap_out]; row_off int64 [n_rows + 1]; host_row uint8 [n_rows]; n_host_rows int64 [>= 2]."""
+        lib = load_prep_library()
+        _require(W, torch.float32)
+        if W.dim() != 2:
+            raise GloveHipError("W must be [n_rows, ld], got %s" % (tuple(W.shape),))
+        n_rows, ld = int(W.shape[0]), int(W.shape[1])
+        _require(word_bytes, torch.uint8); _require(word_off, torch.int64, n_rows + 1); _require(out, torch.uint8)
+        _require(row_off, torch.int64, n_rows + 1); _require(host_row, torch.uint8, n_rows); _require(n_host_rows, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_vectors_format_workspace_bytes(n_rows, int(d)), "glove_vectors_format_workspace_bytes")
+        _check(lib.glove_vectors_format_f32(_ptr(W) if n_rows else None, n_rows, int(d), ld, int(precision), _ptr(word_bytes),
+                                            _ptr(word_off), _ptr(out) if out.numel() else None, _ptr(row_off),
+                                            _ptr(host_row) if n_rows else None, _ptr(n_host_rows), int(out.numel()), _ptr(ws),
+                                            ws.numel(), _stream()), "glove_vectors_format_f32")
+
+    def vectors_lines(self, block: torch.Tensor):
+        """(line_start int32, line_fields int32): the records of a block of bytes, in order — the offset of each record's word
+        and its number of fields, the word included (one host sync for the size)."""
+        cap = (int(block.numel()) + 1) // 2         # the most records the bytes can hold
+        line_start = torch.empty(cap, dtype=torch.int32, device=block.device)
+        line_fields = torch.empty_like(line_start)
+        sizes = torch.zeros(2, dtype=torch.int64, device=block.device)
+        self.vectors_lines_enqueue(block, line_start, line_fields, sizes)
+        m = int(sizes[0].item())
+        return line_start[:m], line_fields[:m]
+
+    def vectors_parse(self, block: torch.Tensor, line_start: torch.Tensor, d: int):
+        """(vec float32 [m, ld], word_len int32 [m], fb_index int64, fb_span int64): fields 1 .. d of every record as
+        np.float32(float(token)), ld = d rounded up to a multiple of four with zero padding columns.  The tokens the device does
+        not parse (and does not write) are listed, sorted by fb_index = record * ld + column, with
+        fb_span = (byte offset << 16) | min(length, VECTORS_MAX_SPAN).  One host sync, a second one where the list was too short."""
+        m, ld = int(line_start.numel()), (int(d) + 3) // 4 * 4
+        line_start = line_start.contiguous()
+        vec = torch.empty((m, ld), dtype=torch.float32, device=block.device)
+        word_len = torch.empty(m, dtype=torch.int32, device=block.device)
+        sizes = torch.tensor([m, 0, 0], dtype=torch.int64).to(block.device)
+        cap_fb = 4096
+        while True:
+            fb_index = torch.empty(cap_fb, dtype=torch.int64, device=block.device)
+            fb_span = torch.empty_like(fb_index)
+            self.vectors_parse_enqueue(block, line_start, sizes[0:1], d, vec, word_len, fb_index, fb_span, sizes[1:3])
+            k = int(sizes[1].item())
+            if k <= cap_fb:
+                break
+            cap_fb = k
+        order = torch.argsort(fb_index[:k])
+        return vec, word_len, fb_index[:k][order], fb_span[:k][order]
+
+    def vectors_format(self, W: torch.Tensor, d: int, precision: int, word_bytes: torch.Tensor, word_off: torch.Tensor, cap_out: int):
+        """(out uint8 [size], row_off int64 [n_rows + 1], host_row uint8 [n_rows]): the text `word v1 ... vd\\n` of every row,
+        values as "%.*f" % (precision, x); rows that hold a NaN, an infinity or |x| >= 2^31 have length 0 and host_row 1.  Raises
+        where the text does not fit cap_out (a row takes at most its word + d (precision + 13) + 1 bytes).  One host sync."""
+        n_rows = int(W.shape[0])
+        out = torch.empty(int(cap_out), dtype=torch.uint8, device=W.device)
+        row_off = torch.empty(n_rows + 1, dtype=torch.int64, device=W.device)
+        host_row = torch.empty(n_rows, dtype=torch.uint8, device=W.device)
+        sizes = torch.zeros(2, dtype=torch.int64, device=W.device)
+        self.vectors_format_enqueue(W, d, precision, word_bytes, word_off, out, row_off, host_row, sizes)
+        size = int(row_off[n_rows].item())
+        if size > cap_out:
+            raise GloveHipError("the text takes %d bytes, capacity %d" % (size, cap_out))
+        return out[:size], row_off, host_row
