@@ -1,6 +1,7 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
 include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h), of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
-include/glove_text_hip.h, include/glove_vectors_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h).
+include/glove_text_hip.h, include/glove_vectors_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h,
+include/glove_factor_dense_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -43,6 +44,9 @@ VECTORS_MAX_SPAN = 65535            # GLOVE_VECTORS_MAX_SPAN: the longest token 
 VECTORS_MAX_D = 65536               # GLOVE_VECTORS_MAX_D: the most numbers per record / columns of a table
 GLOVE_FACTOR_ABI_VERSION = 1        # include/glove_factor_hip.h (libglove_factor_hip.so)
 FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one lane group of glove_csr_spmm_f32 sums
+GLOVE_FACTOR_DENSE_ABI_VERSION = 1  # include/glove_factor_dense_hip.h: the same library's second header (dense tables), versioned on its own
+GRAM_CHUNK = 1024                   # GLOVE_GRAM_CHUNK: rows of one float32 fmaf chain of glove_gram_f64
+GRAM_SLICE = 16384                  # GLOVE_GRAM_SLICE: rows whose chunk partials one float64 slice partial adds
 REWEIGHT_KINDS = {"none": 0, "sqrt": 1, "log1p": 2, "ppmi": 3}      # GLOVE_REWEIGHT_*
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
@@ -107,6 +111,9 @@ VECTORS_EXPORTED_SYMBOLS = ("glove_vectors_abi_version", "glove_vectors_lines_wo
 # every symbol include/glove_factor_hip.h declares (libglove_factor_hip.so)
 FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace_bytes", "glove_csr_spmm_f32",
                            "glove_csr_row_sums_f64", "glove_coo_reweight_f32")
+# every symbol include/glove_factor_dense_hip.h declares (the same library)
+FACTOR_DENSE_EXPORTED_SYMBOLS = ("glove_factor_dense_abi_version", "glove_gram_workspace_bytes", "glove_col_sums_f64",
+                                 "glove_gram_f64", "glove_rows_transform_f32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -332,16 +339,31 @@ def factor_prototypes() -> dict:
     }
 
 
+def factor_dense_prototypes() -> dict:
+    """name -> (result, arguments) of every function include/glove_factor_dense_hip.h declares."""
+    sz, i32, i64, vp = C.c_size_t, C.c_int32, C.c_int64, C.c_void_p
+    return {
+        "glove_factor_dense_abi_version": (C.c_int, []),
+        "glove_gram_workspace_bytes": (sz, [i64, i32]),
+        "glove_col_sums_f64": (C.c_int, [vp, i64, i32, vp, vp, sz, vp]),
+        "glove_gram_f64": (C.c_int, [vp, i64, i32, vp, vp, vp, sz, vp]),
+        "glove_rows_transform_f32": (C.c_int, [vp, i64, i32, vp, i32, vp, vp, vp]),
+    }
+
+
 def load_factor_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_factor_hip.so (include/glove_factor_hip.h) and declare the prototypes, at the first call that needs
-    it: training never loads it.  Raises if it is not built, like load_library."""
+    """dlopen libglove_factor_hip.so (include/glove_factor_hip.h, include/glove_factor_dense_hip.h) and declare the
+    prototypes, at the first call that needs it: training never loads it.  Raises if it is not built, like load_library."""
     global _factor_lib
     if _factor_lib is not None and path is None:
         return _factor_lib
-    lib = _open(Path(path) if path else FACTOR_LIB_PATH, factor_prototypes())
+    lib = _open(Path(path) if path else FACTOR_LIB_PATH, dict(factor_prototypes(), **factor_dense_prototypes()))
     if lib.glove_factor_abi_version() != GLOVE_FACTOR_ABI_VERSION:
         raise GloveHipError("ABI mismatch: factor library %d, binding %d"
                             % (lib.glove_factor_abi_version(), GLOVE_FACTOR_ABI_VERSION))
+    if lib.glove_factor_dense_abi_version() != GLOVE_FACTOR_DENSE_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: factor library (dense entry points) %d, binding %d"
+                            % (lib.glove_factor_dense_abi_version(), GLOVE_FACTOR_DENSE_ABI_VERSION))
     if path is None:
         _factor_lib = lib
     return lib
@@ -1538,6 +1560,55 @@ class GloveHip:
                                                             _ptr(row_sums), _ptr(col_weights), float(total), float(log_shift),
                                                             _ptr(out), _stream()), "glove_coo_reweight_f32")
         return out
+
+    # ---- post-processing of a finished table (include/glove_factor_dense_hip.h): what trainer.postprocess drives
+    def _dense_args(self, X: torch.Tensor, what: str):
+        _require(X, torch.float32)
+        if X.dim() != 2:
+            raise GloveHipError("%s: expected a table [n, d], got %s" % (what, tuple(X.shape)))
+        n, d = int(X.shape[0]), int(X.shape[1])
+        lib = load_factor_library()
+        need = lib.glove_gram_workspace_bytes(n, d)
+        if need == 0:
+            raise GloveHipError("%s takes 1 <= n <= 2^31 - 1 and d %% 4 == 0 in [4, 1024]: got n = %d, d = %d" % (what, n, d))
+        return lib, n, d, need
+
+    def col_sums(self, X: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
+        """The column sums of X [n, d] float32 in float64 [d], in a fixed order (bitwise repeatable)."""
+        lib, n, d, need = self._dense_args(X, "col_sums")
+        ws = torch.empty(need, dtype=torch.uint8, device=X.device) if ws is None else ws
+        sums = torch.empty(d, dtype=torch.float64, device=X.device)
+        _check(lib.glove_col_sums_f64(_ptr(X), n, d, _ptr(sums), _ptr(ws), ws.numel(), _stream()), "glove_col_sums_f64")
+        return sums
+
+    def gram(self, X: torch.Tensor, mean: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> torch.Tensor:
+        """G [d, d] float64 = X~^T X~ for X [n, d] float32, X~ = the float32 difference X - mean (mean float32 [d], or
+        None: X itself): float32 fmaf chains over chunks of GRAM_CHUNK rows, added in float64.  Exactly symmetric and
+        bitwise repeatable (no float atomics)."""
+        lib, n, d, need = self._dense_args(X, "gram")
+        _require(mean, torch.float32, d)
+        ws = torch.empty(need, dtype=torch.uint8, device=X.device) if ws is None else ws
+        G = torch.empty(d, d, dtype=torch.float64, device=X.device)
+        _check(lib.glove_gram_f64(_ptr(X), n, d, _ptr(mean), _ptr(G), _ptr(ws), ws.numel(), _stream()), "glove_gram_f64")
+        return G
+
+    def rows_transform(self, X: torch.Tensor, T: torch.Tensor, shift: torch.Tensor | None = None,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+        """Y [n, m] float32 = X T^T - shift for X [n, d] and T [m, d] float32 (m % 4 == 0 up to 1024; shift float32 [m]
+        or None): a k-ordered fmaf chain per entry, the shift subtracted once.  `out` must not be X."""
+        lib, n, d, _ = self._dense_args(X, "rows_transform")
+        _require(T, torch.float32)
+        if T.dim() != 2 or T.shape[1] != d:
+            raise GloveHipError("expected T [m, d = %d], got %s" % (d, tuple(T.shape)))
+        m = int(T.shape[0])
+        if m < 4 or m > 1024 or m % 4:
+            raise GloveHipError("rows_transform takes m %% 4 == 0 in [4, 1024]: got m = %d" % m)
+        _require(shift, torch.float32, m)
+        Y = torch.empty(n, m, dtype=torch.float32, device=X.device) if out is None else out
+        _require(Y, torch.float32, n * m)
+        _check(lib.glove_rows_transform_f32(_ptr(X), n, d, _ptr(T), m, _ptr(shift), _ptr(Y), _stream()),
+               "glove_rows_transform_f32")
+        return Y
 
     # ---- data prep
     def cooccurrence(self, tokens: torch.Tensor, V: int, context: int, cap: int | None = None):
