@@ -13,6 +13,7 @@
 //   merge_tiles<1>    the same walk with the counts beside the keys; outputs go to LDS at their rank and leave in 16-B stores.
 #include "glove_common.h"
 #include "glove_merge_path.h"
+#include "glove_cooc_finalize.h"
 #include "../../include/glove_cooc_stream_hip.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -243,22 +244,14 @@ static MergeWs carve_merge_ws(void *ws, int64_t cap_a, int64_t cap_b)
 }
 
 // ---- finalize --------------------------------------------------------------------------------------------------------
-// flag[i] = 1 where a new (a, b) starts whose count reaches min_count (at most `context` keys share one (a, b))
+// (the head rule, the pair's sums and the workspace are glove_cooc_finalize.h's: glove_cooc_options.hip weights them otherwise)
 __global__ void finalize_mark(const uint64_t *__restrict__ keys, const int64_t *__restrict__ counts,
                               const int64_t *__restrict__ n, int64_t cap_keys, int32_t context, int64_t min_count,
                               int64_t *__restrict__ flag)
 {
     const int64_t m = clamp_count(n, cap_keys);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t ab = keys[i] / context;
-        int64_t f = 0;
-        if (i == 0 || keys[i - 1] / context != ab) {
-            int64_t cnt = 0;
-            for (int64_t j = i; j < m && j < i + context && keys[j] / context == ab; ++j) cnt += counts[j];
-            f = cnt >= min_count ? 1 : 0;
-        }
-        flag[i] = f;
-    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
+        flag[i] = finalize_head_flag(keys, counts, m, i, context, min_count);
 }
 
 // incl = the inclusive scan of flag: entry i is a written head where flag is set, at output position incl[i] - 1
@@ -273,15 +266,9 @@ __global__ void finalize_aggregate(const uint64_t *__restrict__ keys, const int6
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
         if (!flag[i]) continue;
         const uint64_t ab = keys[i] / context;
-        int64_t cnt = 0;
-        double val = 0.0;
-        for (int64_t j = i; j < m && j < i + context; ++j) {
-            const uint64_t key = keys[j];
-            if (key / context != ab) break;
-            const int k = (int)(key % context) + 1;
-            cnt += counts[j];
-            val += (double)counts[j] / (double)k;
-        }
+        int64_t cnt;
+        double val;
+        finalize_pair<kWindowHarmonic>(keys, counts, m, i, context, cnt, val);
         const int64_t o = incl[i] - 1;
         if (o < cap) {
             out_row[o] = (int32_t)(ab / V);
@@ -291,33 +278,6 @@ __global__ void finalize_aggregate(const uint64_t *__restrict__ keys, const int6
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *out_nnz = m > 0 ? incl[m - 1] : 0;
-}
-
-struct FinalizeWs {
-    int64_t *flag, *incl;
-    void *prim;
-    size_t prim_bytes, bytes;
-};
-
-static FinalizeWs carve_finalize_ws(void *ws, int64_t cap_keys)
-{
-    FinalizeWs w;
-    size_t off = 0;
-    char *base = (char *)ws;
-    auto take = [&](size_t bytes) { void *q = base + off; off += align_up(bytes, 256); return q; };
-    const size_t n = (size_t)(cap_keys > 0 ? cap_keys : 1);
-    w.flag = (int64_t *)take(n * 8);
-    w.incl = (int64_t *)take(n * 8);
-    w.prim_bytes = (size_t)(1u << 20) + n / 16;
-    w.prim = take(w.prim_bytes);
-    w.bytes = off;
-    return w;
-}
-
-static bool bad_key_shape(int32_t V, int32_t context)
-{
-    if (V <= 0 || context <= 0 || context > 255) return true;
-    return (double)V * (double)V * (double)context >= 9.0e18;      // key must fit 63 bits
 }
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
@@ -425,9 +385,7 @@ int glove_cooc_finalize(const uint64_t *keys, const int64_t *counts, const int64
                         int32_t context, int64_t min_count, int32_t *out_row, int32_t *out_col, int64_t *out_count,
                         double *out_value, int64_t *out_nnz, int64_t cap_out, void *ws, size_t ws_bytes, void *stream)
 {
-    if (cap_keys < 0 || cap_keys > kMaxStateCap || bad_key_shape(V, context) || cap_out < 0 || !n || !out_nnz || !ws)
-        return GLOVE_E_BADARG;
-    if ((cap_keys > 0 && (!keys || !counts)) || (cap_out > 0 && (!out_row || !out_col || !out_count || !out_value)))
+    if (finalize_bad_args(keys, counts, n, cap_keys, V, context, out_row, out_col, out_count, out_value, out_nnz, cap_out, ws))
         return GLOVE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
     if (cap_keys == 0) {

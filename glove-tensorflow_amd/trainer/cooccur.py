@@ -21,13 +21,21 @@ occurrences) and merges it into the running one (`VocabAccumulator`); the host c
 alone and reads their strings back from the file; pass two tokenizes again, looks every token's hash up in the kept
 table, compares the bytes, and the ids go to `CoocAccumulator` without touching the host (`process_corpus`).  pandas
 writes the CSV.
+
+Preprocessing options (Levy, Goldberg & Dagan 2015: `sub`, `del`, `dyn`; include/glove_cooc_options_hip.h): `--subsample T`
+and `--delete-unknown` remove tokens from the id stream before the window is laid (`filter_blocks`: a token's fate is a
+hash of its position in the whole stream against its word's threshold, so it does not depend on the blocks or chunks),
+`--window-weighting` chooses how the state's per-distance counts make a pair's `value`.  At their defaults nothing runs
+that did not run before and the files are the same bytes; otherwise `prep.json` says how the files were made.
 """
 from __future__ import annotations
 
+import json
 import logging
 import sys
 from argparse import ArgumentParser
 from collections import Counter
+from pathlib import Path
 
 import numpy as np
 
@@ -108,6 +116,71 @@ def iter_chunks(id_blocks, chunk_tokens: int, context: int):
         buf = buf[own:]
 
 
+KEEP_ALWAYS = 0xFFFFFFFF
+WINDOW_WEIGHTINGS = ("harmonic", "uniform", "dynamic")
+
+
+def stream_counts(vocab) -> np.ndarray:
+    """How often every id occurs in the id stream, from the vocabulary (tokens, counts, ...): a word's own count, and for
+    id 0 everything out of vocabulary as well — the tokens no entry of the lookup table matches are numbered 0, whichever
+    word sits there ("<UNK>" itself wherever it is the most frequent entry)."""
+    tokens, counts = vocab[0], np.asarray(vocab[1], np.int64).copy()
+    unk = tokens.index("<UNK>")
+    if unk != 0:
+        counts[0] += counts[unk]
+        counts[unk] = 0
+    return counts
+
+
+def subsample_thresholds(counts, subsample: float = 0.0, delete_unknown: bool = False) -> np.ndarray:
+    """The uint32 [V] table `filter_blocks` takes (the keep rule of include/glove_cooc_options_hip.h), made once on the
+    host in float64 from the ids' stream counts: a token of id w is kept with probability q(w) = min(1, sqrt(T / f_w)),
+    f_w = counts[w] / sum(counts) (word2vec's -sample, hyperwords' `sub`); the entry is 0xFFFFFFFF where q >= 1 (always
+    kept), otherwise floor(q 2^32).  T = 0 keeps everything.  delete_unknown: thresholds[0] = 0, id 0 always goes."""
+    counts = np.asarray(counts, np.int64)
+    subsample = float(subsample)
+    if not (np.isfinite(subsample) and 0.0 <= subsample < 1.0):
+        raise ValueError("subsample must be finite and in [0, 1), got %r" % (subsample,))
+    thresholds = np.full(len(counts), KEEP_ALWAYS, np.uint32)
+    total = int(counts.sum())
+    if subsample > 0.0 and total > 0:
+        seen = counts > 0
+        q = np.ones(len(counts), np.float64)
+        q[seen] = np.sqrt(np.float64(subsample) / (counts[seen].astype(np.float64) / np.float64(total)))
+        drop = q < 1.0
+        thresholds[drop] = np.minimum(np.floor(q[drop] * 4294967296.0), np.float64(KEEP_ALWAYS)).astype(np.uint32)
+    if delete_unknown and len(thresholds):
+        thresholds[0] = 0
+    return thresholds
+
+
+def filter_blocks(id_blocks, thresholds, seed, backend, totals=None):
+    """Sits between the id blocks and `iter_chunks`: every block's survivors under the keep rule of
+    include/glove_cooc_options_hip.h (`backend.token_filter(ids, pos0, thresholds, seed)`; GloveHip is the product
+    backend), removed BEFORE the window is laid — distances shrink across removed tokens.  A token's fate depends on its id
+    and its position in the whole stream (the running `pos0` kept here), never on where the blocks were cut.  Host arrays
+    go to the backend's device where it has one; device tensors stay where they are.  `totals`, a dict, receives the
+    tokens "read" and "kept"."""
+    thresholds = np.ascontiguousarray(thresholds, np.uint32)
+    if hasattr(backend, "device"):
+        import torch
+        thresholds = torch.from_numpy(thresholds.view(np.int32).copy()).to(backend.device)
+    pos = kept = 0
+    for ids in id_blocks:
+        if isinstance(ids, np.ndarray) and hasattr(backend, "device"):
+            import torch
+            ids = torch.from_numpy(np.ascontiguousarray(ids, np.int32)).to(backend.device)
+        out = backend.token_filter(ids, pos, thresholds, int(seed))
+        pos += len(ids)
+        kept += len(out)
+        if totals is not None:
+            totals["read"], totals["kept"] = pos, kept
+        if len(out):
+            yield out
+    if totals is not None:
+        totals["read"], totals["kept"] = pos, kept
+
+
 def _resized(like, n):
     """An uninitialised 1-d array of n elements of `like`'s kind (a torch tensor on its device, or numpy)."""
     return like.new_empty(n) if hasattr(like, "new_empty") else np.empty(n, like.dtype)
@@ -123,6 +196,7 @@ class CoocAccumulator:
         cooc_chunk_keys(tokens, n_own, V, context) -> (keys, counts)
         cooc_merge(keys_a, counts_a, keys_b, counts_b, keys_out, counts_out) -> (keys, counts)    views of the outputs
         cooc_finalize(keys, counts, V, context, min_count) -> (row, col, count, value)
+            (and `weighting=` where another window weighting than the harmonic one is asked for)
     A backend with a `device` gets numpy tokens moved there."""
 
     def __init__(self, V: int, context: int, backend):
@@ -157,11 +231,18 @@ class CoocAccumulator:
         self.keys, self.counts = self.backend.cooc_merge(self.keys, self.counts, keys, counts, *self._back)
         self._front, self._back = self._back, self._front
 
-    def finalize(self, min_count: int = 0):
-        """(row, col, count, value) in (row, col) order, pairs with count >= min_count only."""
+    def finalize(self, min_count: int = 0, weighting: str = "harmonic"):
+        """(row, col, count, value) in (row, col) order, pairs with count >= min_count only.  The state keeps the
+        distances, so the window's weighting is chosen here: "harmonic" (value = sum count / distance), "uniform"
+        (value = count) or "dynamic" (value = sum count (context - distance + 1) / context, the expected weight under
+        word2vec's uniformly drawn window size)."""
         if self.keys is None:
             raise ValueError("no chunk was added")
-        return self.backend.cooc_finalize(self.keys, self.counts, self.V, self.context, int(min_count))
+        if weighting not in WINDOW_WEIGHTINGS:
+            raise ValueError("weighting must be one of %s, got %r" % (", ".join(WINDOW_WEIGHTINGS), weighting))
+        if weighting == "harmonic":
+            return self.backend.cooc_finalize(self.keys, self.counts, self.V, self.context, int(min_count))
+        return self.backend.cooc_finalize(self.keys, self.counts, self.V, self.context, int(min_count), weighting=weighting)
 
 
 class VocabAccumulator:
@@ -303,8 +384,16 @@ def count_vocabulary(path, block_bytes: int = BLOCK_BYTES) -> Counter:
 
 
 def process_corpus(path, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, chunk_tokens=CHUNK_TOKENS,
-                   count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python"):
+                   count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python",
+                   subsample: float = 0.0, subsample_seed: int = 0, delete_unknown: bool = False,
+                   window_weighting: str = "harmonic"):
     """The data `trainer.text8.save_data` writes, from a corpus file of any length.
+
+    subsample = T > 0 keeps a token of word w with probability min(1, sqrt(T / f_w)) and delete_unknown removes the
+    out-of-vocabulary tokens (id 0), both BEFORE the window is laid (`filter_blocks`); window_weighting chooses how a
+    pair's distances make its `value` (`CoocAccumulator.finalize`).  The vocabulary is the raw corpus's in every case.
+    With all four at their defaults no filter runs and the data are what they were without them; otherwise the result
+    also holds "prep": the options, the tokens read and the tokens kept.
 
     tokenizer="python" counts the vocabulary and maps tokens to ids on the host (`Counter`, `dict`); "device" does both on
     the backend (include/glove_text_hip.h) and returns the same data.  Why it is the same whenever it returns (it raises
@@ -318,6 +407,11 @@ def process_corpus(path, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=
     from trainer import text8
     if tokenizer not in ("python", "device"):
         raise ValueError("tokenizer must be 'python' or 'device', got %r" % (tokenizer,))
+    if window_weighting not in WINDOW_WEIGHTINGS:
+        raise ValueError("window_weighting must be one of %s, got %r" % (", ".join(WINDOW_WEIGHTINGS), window_weighting))
+    subsample = float(subsample)
+    if not (np.isfinite(subsample) and 0.0 <= subsample < 1.0):
+        raise ValueError("subsample must be finite and in [0, 1), got %r" % (subsample,))
     if backend is None:
         from trainer.hip_api import GloveHip
         backend = GloveHip("cuda:0")
@@ -333,23 +427,42 @@ def process_corpus(path, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=
     else:
         id_blocks = (np.fromiter((lookup.get(t, 0) for t in tokens), dtype=np.int32, count=len(tokens))
                      for tokens in iter_token_blocks(path, block_bytes))
+    totals = {}
+    if subsample > 0.0 or delete_unknown:
+        thresholds = subsample_thresholds(stream_counts(vocab), subsample, delete_unknown)
+        id_blocks = filter_blocks(id_blocks, thresholds, subsample_seed, backend, totals)
     for piece, n_own in iter_chunks(id_blocks, chunk_tokens, context_size):
         acc.add(piece, n_own)
         logger.info("chunk %d: %d keys in the state.", acc.chunks, len(acc))
     if acc.keys is None:
         acc.add(np.zeros(0, np.int32), 0)       # an empty corpus
-    arrays = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in acc.finalize(count_minimum)]
+    arrays = [np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in acc.finalize(count_minimum, window_weighting)]
     logger.info("after the count filter: %d pairs.", len(arrays[0]))
     table = text8.interaction_columns(*arrays, vocab, seed)
-    return {"vocabulary": vocab, "interaction": text8.create_glove_table(table, count_minimum)}
+    data = {"vocabulary": vocab, "interaction": text8.create_glove_table(table, count_minimum)}
+    if subsample > 0.0 or subsample_seed != 0 or delete_unknown or window_weighting != "harmonic":
+        read = int(np.asarray(vocab[1], np.int64).sum())
+        data["prep"] = {"subsample": subsample, "subsample_seed": int(subsample_seed), "delete_unknown": bool(delete_unknown),
+                        "window_weighting": window_weighting, "tokens_read": int(totals.get("read", read)),
+                        "tokens_kept": int(totals.get("kept", read))}
+        logger.info("kept %d of %d tokens.", data["prep"]["tokens_kept"], data["prep"]["tokens_read"])
+    return data
 
 
 def main(corpus, dest, vocab_size=VOCAB_SIZE, coverage=COVERAGE, context_size=CONTEXT_SIZE, chunk_tokens=CHUNK_TOKENS,
-         count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python", **kwargs):
+         count_minimum=10, seed=0, backend=None, block_bytes: int = BLOCK_BYTES, tokenizer: str = "python",
+         subsample: float = 0.0, subsample_seed: int = 0, delete_unknown: bool = False, window_weighting: str = "harmonic",
+         **kwargs):
+    """Writes vocab.csv, vocab.txt and interaction.csv to `dest`; with any of the four preprocessing options set, also
+    prep.json (the options, the tokens read and kept), so the files say how they were made."""
     from trainer import text8
     data = process_corpus(corpus, vocab_size, coverage, context_size, chunk_tokens, count_minimum, seed, backend=backend,
-                          block_bytes=block_bytes, tokenizer=tokenizer)
-    return text8.save_data(data, dest)
+                          block_bytes=block_bytes, tokenizer=tokenizer, subsample=subsample, subsample_seed=subsample_seed,
+                          delete_unknown=delete_unknown, window_weighting=window_weighting)
+    text8.save_data(data, dest)
+    if "prep" in data:
+        (Path(dest) / "prep.json").write_text(json.dumps(data["prep"], indent=2, sort_keys=True) + "\n")
+    return data
 
 
 if __name__ == "__main__":
@@ -367,6 +480,15 @@ if __name__ == "__main__":
     parser.add_argument("--tokenizer", choices=("python", "device"), default="python",
                         help="where the corpus is split into tokens, counted and numbered: on the host, or on the GPU from "
                              "the file's bytes (the same files)" + d)
+    parser.add_argument("--subsample", type=float, default=0.0, metavar="T",
+                        help="keep a token of word w with probability min(1, sqrt(T / f_w)), f_w its share of all tokens, "
+                             "before the window is laid; 0 keeps every token" + d)
+    parser.add_argument("--subsample-seed", type=int, default=0, help="seed of the subsampling decisions" + d)
+    parser.add_argument("--delete-unknown", action="store_true",
+                        help="remove the out-of-vocabulary tokens (id 0) before the window is laid")
+    parser.add_argument("--window-weighting", choices=WINDOW_WEIGHTINGS, default="harmonic",
+                        help="a pair's value from its counts per distance k: sum count / k, count, or "
+                             "sum count (window - k + 1) / window" + d)
     args = parser.parse_args()
     logger.info("call: %s.", " ".join(sys.argv))
     try:

@@ -1,7 +1,7 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
 include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h), of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
-include/glove_text_hip.h, include/glove_vectors_hip.h) and of libglove_factor_hip.so (include/glove_factor_hip.h,
-include/glove_factor_dense_hip.h).
+include/glove_text_hip.h, include/glove_vectors_hip.h, include/glove_cooc_options_hip.h) and of libglove_factor_hip.so
+(include/glove_factor_hip.h, include/glove_factor_dense_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -42,6 +42,9 @@ GLOVE_VECTORS_ABI_VERSION = 1       # include/glove_vectors_hip.h: the same libr
 VECTORS_TILE_BYTES = 4096           # GLOVE_VECTORS_TILE_BYTES: bytes of a block one workgroup of glove_vectors_lines_u8 owns
 VECTORS_MAX_SPAN = 65535            # GLOVE_VECTORS_MAX_SPAN: the longest token length a fallback span holds
 VECTORS_MAX_D = 65536               # GLOVE_VECTORS_MAX_D: the most numbers per record / columns of a table
+GLOVE_COOC_OPTIONS_ABI_VERSION = 1  # include/glove_cooc_options_hip.h: the same library's fourth header (token filter, window weightings), versioned on its own
+FILTER_TILE = 4096                  # GLOVE_FILTER_TILE: tokens of a block one workgroup of glove_token_filter_i32 owns
+WINDOW_WEIGHTINGS = {"harmonic": 0, "uniform": 1, "dynamic": 2}      # GLOVE_WINDOW_*
 GLOVE_FACTOR_ABI_VERSION = 1        # include/glove_factor_hip.h (libglove_factor_hip.so)
 FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one lane group of glove_csr_spmm_f32 sums
 GLOVE_FACTOR_DENSE_ABI_VERSION = 1  # include/glove_factor_dense_hip.h: the same library's second header (dense tables), versioned on its own
@@ -108,6 +111,9 @@ TEXT_EXPORTED_SYMBOLS = ("glove_text_abi_version", "glove_text_tokenize_workspac
 # every symbol include/glove_vectors_hip.h declares (the same library)
 VECTORS_EXPORTED_SYMBOLS = ("glove_vectors_abi_version", "glove_vectors_lines_workspace_bytes", "glove_vectors_lines_u8",
                             "glove_vectors_parse_f32", "glove_vectors_format_workspace_bytes", "glove_vectors_format_f32")
+# every symbol include/glove_cooc_options_hip.h declares (the same library)
+COOC_OPTIONS_EXPORTED_SYMBOLS = ("glove_cooc_options_abi_version", "glove_token_filter_workspace_bytes", "glove_token_filter_i32",
+                                 "glove_cooc_finalize_weighted_workspace_bytes", "glove_cooc_finalize_weighted")
 # every symbol include/glove_factor_hip.h declares (libglove_factor_hip.so)
 FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace_bytes", "glove_csr_spmm_f32",
                            "glove_csr_row_sums_f64", "glove_coo_reweight_f32")
@@ -280,7 +286,7 @@ _prep_lib = None
 
 
 def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h, include/glove_vectors_hip.h) and declare the prototypes, at the first call that needs
+    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h, include/glove_vectors_hip.h, include/glove_cooc_options_hip.h) and declare the prototypes, at the first call that needs
     it: training never loads it.  Raises if it is not built, like load_library."""
     global _prep_lib
     if _prep_lib is not None and path is None:
@@ -308,6 +314,11 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_vectors_parse_f32": (C.c_int, [vp, i64, vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
         "glove_vectors_format_workspace_bytes": (sz, [i64, i32]),
         "glove_vectors_format_f32": (C.c_int, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_cooc_options_abi_version": (C.c_int, []),
+        "glove_token_filter_workspace_bytes": (sz, [i64]),
+        "glove_token_filter_i32": (C.c_int, [vp, i64, i64, vp, i32, C.c_uint64, vp, vp, i64, vp, sz, vp]),
+        "glove_cooc_finalize_weighted_workspace_bytes": (sz, [i64]),
+        "glove_cooc_finalize_weighted": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
     }
     lib = _open(Path(path) if path else PREP_LIB_PATH, protos)
     if lib.glove_cooc_stream_abi_version() != GLOVE_COOC_STREAM_ABI_VERSION:
@@ -319,6 +330,9 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_vectors_abi_version() != GLOVE_VECTORS_ABI_VERSION:
         raise GloveHipError("ABI mismatch: prep library (word-vector entry points) %d, binding %d"
                             % (lib.glove_vectors_abi_version(), GLOVE_VECTORS_ABI_VERSION))
+    if lib.glove_cooc_options_abi_version() != GLOVE_COOC_OPTIONS_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: prep library (counting-option entry points) %d, binding %d"
+                            % (lib.glove_cooc_options_abi_version(), GLOVE_COOC_OPTIONS_ABI_VERSION))
     if path is None:
         _prep_lib = lib
     return lib
@@ -1665,15 +1679,26 @@ class GloveHip:
                                         cap_b, _ptr(keys_out), _ptr(counts_out), _ptr(n_out), int(keys_out.numel()),
                                         _ptr(ws), ws.numel(), _stream()), "glove_cooc_merge_u64")
 
-    def cooc_finalize_enqueue(self, keys, counts, n, V: int, context: int, min_count: int, row, col, cnt, val, nnz, ws=None):
-        """glove_cooc_finalize on the current stream, nothing read back; n and nnz are int64 device tensors (nnz [>= 2])."""
+    def cooc_finalize_enqueue(self, keys, counts, n, V: int, context: int, min_count: int, row, col, cnt, val, nnz, ws=None,
+                              weighting: str = "harmonic"):
+        """glove_cooc_finalize on the current stream, nothing read back; n and nnz are int64 device tensors (nnz [>= 2]).
+        Another `weighting` than the default ("uniform", "dynamic") goes to glove_cooc_finalize_weighted
+        (include/glove_cooc_options_hip.h); the workspace is the same."""
         lib = load_prep_library()
+        if weighting not in WINDOW_WEIGHTINGS:
+            raise GloveHipError("weighting must be one of %s, got %r" % (sorted(WINDOW_WEIGHTINGS), weighting))
         _require(keys, torch.int64); _require(counts, torch.int64, int(keys.numel())); _require(n, torch.int64)
         cap = int(row.numel())
         _require(row, torch.int32); _require(col, torch.int32, cap); _require(cnt, torch.int64, cap)
         _require(val, torch.float64, cap); _require(nnz, torch.int64)
         if ws is None:
             ws = self._bytes(lib.glove_cooc_finalize_workspace_bytes(int(keys.numel())), "glove_cooc_finalize_workspace_bytes")
+        if weighting != "harmonic":
+            _check(lib.glove_cooc_finalize_weighted(_ptr(keys), _ptr(counts), _ptr(n), int(keys.numel()), V, context,
+                                                    int(min_count), WINDOW_WEIGHTINGS[weighting], _ptr(row), _ptr(col), _ptr(cnt),
+                                                    _ptr(val), _ptr(nnz), cap, _ptr(ws), ws.numel(), _stream()),
+                   "glove_cooc_finalize_weighted")
+            return
         _check(lib.glove_cooc_finalize(_ptr(keys), _ptr(counts), _ptr(n), int(keys.numel()), V, context, int(min_count),
                                        _ptr(row), _ptr(col), _ptr(cnt), _ptr(val), _ptr(nnz), cap, _ptr(ws), ws.numel(),
                                        _stream()), "glove_cooc_finalize")
@@ -1705,9 +1730,11 @@ class GloveHip:
             raise GloveHipError("the merged table has %d keys, capacity %d" % (m, keys_out.numel()))
         return keys_out[:m], counts_out[:m]
 
-    def cooc_finalize(self, keys, counts, V: int, context: int, min_count: int = 0, cap: int | None = None):
+    def cooc_finalize(self, keys, counts, V: int, context: int, min_count: int = 0, cap: int | None = None,
+                      weighting: str = "harmonic"):
         """(row i32, col i32, count i64, value f64) sorted by (row, col) from a key table: what `cooccurrence` returns for
-        the corpus the keys were counted from, bit for bit, cut to the pairs with count >= min_count (one host sync)."""
+        the corpus the keys were counted from, bit for bit, cut to the pairs with count >= min_count (one host sync).
+        weighting "uniform": value = count; "dynamic": value = sum_k n_k (context - k + 1) / context."""
         n = int(keys.numel())
         cap = int(cap if cap is not None else max(1, n))
         dev = keys.device
@@ -1716,11 +1743,36 @@ class GloveHip:
         cnt = torch.empty(cap, dtype=torch.int64, device=dev)
         val = torch.empty(cap, dtype=torch.float64, device=dev)
         sizes = torch.tensor([n, 0, 0], dtype=torch.int64).to(dev)
-        self.cooc_finalize_enqueue(keys, counts, sizes[0:1], V, context, min_count, row, col, cnt, val, sizes[1:3])
+        self.cooc_finalize_enqueue(keys, counts, sizes[0:1], V, context, min_count, row, col, cnt, val, sizes[1:3],
+                                   weighting=weighting)
         m = int(sizes[1].item())
         if m > cap:
             raise GloveHipError("co-occurrence table has %d entries, capacity %d" % (m, cap))
         return row[:m], col[:m], cnt[:m], val[:m]
+
+    # ---- removing tokens before the window is laid (include/glove_cooc_options_hip.h): what trainer.cooccur.filter_blocks drives
+    def token_filter_enqueue(self, ids, pos0: int, thresholds, seed: int, ids_out, n_out, ws=None):
+        """glove_token_filter_i32 on the current stream, nothing read back: ids int32 [n], thresholds int32 [V] (the bits of
+        the header's uint32), ids_out int32 [cap], n_out an int64 device tensor ([>= 2] where the block may be empty)."""
+        lib = load_prep_library()
+        _require(ids, torch.int32); _require(thresholds, torch.int32); _require(ids_out, torch.int32); _require(n_out, torch.int64)
+        n = int(ids.numel())
+        if ws is None:
+            ws = self._bytes(lib.glove_token_filter_workspace_bytes(n), "glove_token_filter_workspace_bytes")
+        _check(lib.glove_token_filter_i32(_ptr(ids), n, int(pos0), _ptr(thresholds), int(thresholds.numel()),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(ids_out), _ptr(n_out), int(ids_out.numel()),
+                                          _ptr(ws), ws.numel(), _stream()), "glove_token_filter_i32")
+
+    def token_filter(self, ids: torch.Tensor, pos0: int, thresholds, seed: int = 0):
+        """The ids that survive the keep rule of include/glove_cooc_options_hip.h, in stream order: the token at index i
+        has the global position pos0 + i.  thresholds: uint32 [V] as a numpy array, or its bits as an int32 device tensor
+        (one host sync for the size)."""
+        if isinstance(thresholds, np.ndarray):
+            thresholds = torch.from_numpy(np.ascontiguousarray(thresholds, np.uint32).view(np.int32).copy()).to(ids.device)
+        out = torch.empty(max(1, int(ids.numel())), dtype=torch.int32, device=ids.device)
+        n_out = torch.zeros(2, dtype=torch.int64, device=ids.device)
+        self.token_filter_enqueue(ids, pos0, thresholds, seed, out, n_out)
+        return out[:int(n_out[0].item())]
 
     # ---- tokenizing and numbering a corpus (include/glove_text_hip.h): what trainer.cooccur drives with --tokenizer device.
     # Hashes and vocabulary keys travel as int64 tensors whose bits are the header's uint64.
