@@ -33,6 +33,9 @@ __device__ inline void stamp(int slot)
 #define GLOVE_DRAIN() ((void)0)
 #endif
 
+// a host function that returns a status hands a failed HIP (or rocPRIM) call's error back as it is
+#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
+
 __host__ __device__ inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Hands out the pieces of a workspace one behind the other, each 256-B aligned; `off` ends as the bytes they take.

@@ -1,6 +1,6 @@
 // The preprocessing options of the corpus-to-counts stage on gfx950 (include/glove_cooc_options_hip.h,
 // libglove_prep_hip.so): a stream compaction of the token ids under a per-position keep decision, and the finalisation of
-// glove_cooc_stream.hip with other distance weightings.
+// glove_table_ops.hip with other distance weightings.
 //
 // The filter reads 4 B per token and writes 4 B per survivor, twice over the input:
 //   filter_tiles<0>   one workgroup per tile of GLOVE_FILTER_TILE tokens: every lane decides four consecutive tokens, a wave
@@ -10,17 +10,13 @@
 //                     survivors go to LDS at their rank and leave at offset[tile] in 16-B stores.
 // The decision is a function of the token's id and its GLOBAL position: nothing depends on the grid, the tile or the block cut.
 #include "glove_common.h"
-#include "glove_merge_path.h"
-#include "glove_cooc_finalize.h"
+#include "glove_table_ops.h"
 #include "../../include/glove_cooc_options_hip.h"
-
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/functional.hpp>
 
 namespace glove {
 
 static_assert(kWindowHarmonic == GLOVE_WINDOW_HARMONIC && kWindowUniform == GLOVE_WINDOW_UNIFORM &&
-              kWindowDynamic == GLOVE_WINDOW_DYNAMIC, "glove_cooc_finalize.h names the header's weightings");
+              kWindowDynamic == GLOVE_WINDOW_DYNAMIC, "glove_table_ops.h names the header's weightings");
 
 // ---- token filter ----------------------------------------------------------------------------------------------------
 constexpr int kFilterTile = GLOVE_FILTER_TILE;            // tokens per workgroup
@@ -142,68 +138,6 @@ __global__ __launch_bounds__(kBlock) void filter_tiles(const int32_t *__restrict
     store_ids(ids_out + off, room < total ? (int)room : total, s_out);
 }
 
-struct FilterWs {
-    int64_t *count, *offset;
-    void *prim;
-    size_t prim_bytes, bytes;
-    int64_t tiles;
-};
-
-static FilterWs carve_filter_ws(void *ws, int64_t n)
-{
-    FilterWs w;
-    size_t off = 0;
-    char *base = (char *)ws;
-    auto take = [&](size_t bytes) { void *q = base + off; off += align_up(bytes, 256); return q; };
-    w.tiles = (n + kFilterTile - 1) / kFilterTile;
-    if (w.tiles < 1) w.tiles = 1;
-    w.count = (int64_t *)take((size_t)w.tiles * 8);
-    w.offset = (int64_t *)take((size_t)w.tiles * 8);
-    w.prim_bytes = (size_t)(64u << 10) + (size_t)w.tiles * 8;
-    w.prim = take(w.prim_bytes);
-    w.bytes = off;
-    return w;
-}
-
-// ---- weighted finalize -----------------------------------------------------------------------------------------------
-// the two kernels of glove_cooc_finalize (glove_cooc_stream.hip) with the pair's value chosen at compile time
-__global__ void weighted_mark(const uint64_t *__restrict__ keys, const int64_t *__restrict__ counts,
-                              const int64_t *__restrict__ n, int64_t cap_keys, int32_t context, int64_t min_count,
-                              int64_t *__restrict__ flag)
-{
-    const int64_t m = clamp_count(n, cap_keys);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x)
-        flag[i] = finalize_head_flag(keys, counts, m, i, context, min_count);
-}
-
-template <int WEIGHTING>
-__global__ void weighted_aggregate(const uint64_t *__restrict__ keys, const int64_t *__restrict__ counts,
-                                   const int64_t *__restrict__ n, int64_t cap_keys, const int64_t *__restrict__ flag,
-                                   const int64_t *__restrict__ incl, int32_t V, int32_t context, int64_t cap,
-                                   int32_t *__restrict__ out_row, int32_t *__restrict__ out_col,
-                                   int64_t *__restrict__ out_count, double *__restrict__ out_value,
-                                   int64_t *__restrict__ out_nnz)
-{
-    const int64_t m = clamp_count(n, cap_keys);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        if (!flag[i]) continue;
-        const uint64_t ab = keys[i] / context;
-        int64_t cnt;
-        double val;
-        finalize_pair<WEIGHTING>(keys, counts, m, i, context, cnt, val);
-        const int64_t o = incl[i] - 1;
-        if (o < cap) {
-            out_row[o] = (int32_t)(ab / V);
-            out_col[o] = (int32_t)(ab % V);
-            out_count[o] = cnt;
-            out_value[o] = val;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *out_nnz = m > 0 ? incl[m - 1] : 0;
-}
-
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 }  // namespace glove
 
 using namespace glove;
@@ -215,7 +149,7 @@ int glove_cooc_options_abi_version(void) { return GLOVE_COOC_OPTIONS_ABI_VERSION
 size_t glove_token_filter_workspace_bytes(int64_t n)
 {
     if (n < 0 || n > kMaxFilterTokens) return 0;
-    return carve_filter_ws(nullptr, n).bytes;
+    return tile_counts_bytes(tiles_of(n, kFilterTile));
 }
 
 int glove_token_filter_i32(const int32_t *ids, int64_t n, int64_t pos0, const uint32_t *thresholds, int32_t V, uint64_t seed,
@@ -235,58 +169,31 @@ int glove_token_filter_i32(const int32_t *ids, int64_t n, int64_t pos0, const ui
                       overlap(ids_out, out_bytes, n_out, 8)))
         return GLOVE_E_BADARG;
     if (overlap(n_out, 8, ids, (size_t)n * 4) || overlap(n_out, 8, thresholds, (size_t)V * 4)) return GLOVE_E_BADARG;
-    const FilterWs w = carve_filter_ws(ws, n);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
-    if (need > w.prim_bytes) return GLOVE_E_WORKSPACE;
+    WsCarver c{(char *)ws};
+    const TileCounts w = carve_tile_counts(c, tiles_of(n, kFilterTile));
+    if (c.off > ws_bytes) return GLOVE_E_WORKSPACE;
+    size_t need;
+    if (const int rc = tile_scan_query(w, need, st)) return rc;
     const uint64_t hash_add = (uint64_t)pos0 + (seed + 1ull) * 0x9E3779B97F4A7C15ull;
     const dim3 grid((unsigned int)w.tiles);
     hipLaunchKernelGGL(filter_tiles<false>, grid, dim3(kBlock), 0, st, ids, n, hash_add, thresholds, V, w.count, w.offset, ids_out,
                        n_out, cap);
-    HIP_TRY(rocprim::exclusive_scan(w.prim, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
+    HIP_TRY(tile_scan(w, w.prim, need, st));
     hipLaunchKernelGGL(filter_tiles<true>, grid, dim3(kBlock), 0, st, ids, n, hash_add, thresholds, V, w.count, w.offset, ids_out,
                        n_out, cap);
     return (int)hipGetLastError();
 }
 
-size_t glove_cooc_finalize_weighted_workspace_bytes(int64_t cap_keys)
-{
-    if (cap_keys < 0 || cap_keys > kMaxStateCap) return 0;
-    return carve_finalize_ws(nullptr, cap_keys).bytes;
-}
+size_t glove_cooc_finalize_weighted_workspace_bytes(int64_t cap_keys) { return finalize_workspace_bytes(cap_keys); }
 
 int glove_cooc_finalize_weighted(const uint64_t *keys, const int64_t *counts, const int64_t *n, int64_t cap_keys, int32_t V,
                                  int32_t context, int64_t min_count, int32_t weighting, int32_t *out_row, int32_t *out_col,
                                  int64_t *out_count, double *out_value, int64_t *out_nnz, int64_t cap_out, void *ws,
                                  size_t ws_bytes, void *stream)
 {
-    if (finalize_bad_args(keys, counts, n, cap_keys, V, context, out_row, out_col, out_count, out_value, out_nnz, cap_out, ws))
-        return GLOVE_E_BADARG;
-    if (weighting != GLOVE_WINDOW_HARMONIC && weighting != GLOVE_WINDOW_UNIFORM && weighting != GLOVE_WINDOW_DYNAMIC)
-        return GLOVE_E_BADARG;
-    hipStream_t st = (hipStream_t)stream;
-    if (cap_keys == 0) {
-        HIP_TRY(zero_words(out_nnz, 2, st));
-        return 0;
-    }
-    const FinalizeWs w = carve_finalize_ws(ws, cap_keys);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    size_t need = 0;
-    HIP_TRY(rocprim::inclusive_scan(nullptr, need, w.flag, w.incl, (size_t)cap_keys, rocprim::plus<int64_t>(), st));
-    if (need > w.prim_bytes) return GLOVE_E_WORKSPACE;
-    const int nb = blocks_for(cap_keys, kBlock);
-    hipLaunchKernelGGL(weighted_mark, dim3(nb), dim3(kBlock), 0, st, keys, counts, n, cap_keys, context, min_count, w.flag);
-    // entries past *n are stale but never read: the aggregation stops at *n
-    HIP_TRY(rocprim::inclusive_scan(w.prim, need, w.flag, w.incl, (size_t)cap_keys, rocprim::plus<int64_t>(), st));
-#define GLOVE_AGGREGATE(W)                                                                                                    \
-    hipLaunchKernelGGL(weighted_aggregate<W>, dim3(nb), dim3(kBlock), 0, st, keys, counts, n, cap_keys, w.flag, w.incl, V, context, \
-                       cap_out, out_row, out_col, out_count, out_value, out_nnz)
-    if (weighting == GLOVE_WINDOW_HARMONIC) GLOVE_AGGREGATE(kWindowHarmonic);
-    else if (weighting == GLOVE_WINDOW_UNIFORM) GLOVE_AGGREGATE(kWindowUniform);
-    else GLOVE_AGGREGATE(kWindowDynamic);
-#undef GLOVE_AGGREGATE
-    return (int)hipGetLastError();
+    // (a weighting the header does not name is refused there, with the other arguments)
+    return finalize_table(keys, counts, n, cap_keys, V, context, min_count, weighting, out_row, out_col, out_count, out_value,
+                          out_nnz, cap_out, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,12 +1,11 @@
-// Device helpers of the merge-path merges of libglove_prep_hip.so: glove_cooc_merge_u64 (glove_cooc_stream.hip) and
-// glove_text_vocab_merge (glove_text.hip).  Inline functions only: every kernel stays in the one object that defines it.
+// Inline helpers that several objects of libglove_prep_hip.so use: the merge-path search, 16-B moves of 8-byte words between
+// memory and LDS, a block scan, a device-side count, an overlap test.  No kernels: a kernel the objects share is compiled
+// once, in glove_table_ops.hip, and reached through a host function (glove_table_ops.h).
 #pragma once
 #include "glove_common.h"
+#include "glove_cooc_keys.h"      // kNoKey
 
 namespace glove {
-
-constexpr uint64_t kNoKey = ~0ull;      // unused key slots hold the sentinel (sorts last); all-ones never appears as a key
-constexpr int64_t kMaxStateCap = (int64_t)1 << 40;
 
 // How many of the first `diag` entries of the merged order (ties to A) come from A.
 template <typename I>

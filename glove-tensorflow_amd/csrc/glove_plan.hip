@@ -963,8 +963,6 @@ static void launch_sorts(const SortPass *fin, const PlanWs *pw, int nb, int64_t 
     }
 }
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 // The tiled builder over nb <= kPlanSetMax batches of B pairs each (batch j: pairs [j B, (j + 1) B) of the arrays, plan
 // plans[j], workspace slice j): every launch covers all of them.
 static int build_tiled_set(const int32_t *row, const int32_t *col, const float *w, const float *y, int64_t B, int32_t V,

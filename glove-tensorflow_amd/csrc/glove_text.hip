@@ -7,11 +7,11 @@
 //   text_emit_tokens    the same flags again; starts numbered by a block scan; every token's start and end written;
 //   text_hash_tokens    one lane per token: length, FNV-1a hash;
 // the block's vocabulary is a stable radix sort of (hash, token index) and a run-length encoding (rocPRIM, as
-// glove_cooc_chunk_keys_i32), two vocabularies are merged by the merge-path merge of glove_cooc_stream.hip with one more
-// payload word, and pass two looks every token's hash up in the sorted table of the kept words and compares the bytes.
+// glove_cooc_chunk_keys_i32), two vocabularies are merged by the merge-path merge of glove_table_ops.hip with `where` as a
+// second payload word, and pass two looks every token's hash up in the sorted table of the kept words and compares the bytes.
 // Integers only; the two counters (tokens too long, hash collisions) are integer atomics.
 #include "glove_common.h"
-#include "glove_merge_path.h"
+#include "glove_table_ops.h"
 #include "../../include/glove_cooc_stream_hip.h"
 #include "../../include/glove_text_hip.h"
 
@@ -150,29 +150,6 @@ __global__ void text_hash_tokens(const uint8_t *__restrict__ bytes, const int32_
     }
 }
 
-struct TokenizeWs {
-    int64_t *count, *offset;
-    void *prim;
-    size_t prim_bytes, bytes;
-    int64_t tiles;
-};
-
-static TokenizeWs carve_tokenize_ws(void *ws, int64_t n_bytes)
-{
-    TokenizeWs w;
-    size_t off = 0;
-    char *base = (char *)ws;
-    auto take = [&](size_t bytes) { void *q = base + off; off += align_up(bytes, 256); return q; };
-    w.tiles = (n_bytes + kTextTile - 1) / kTextTile;
-    if (w.tiles < 1) w.tiles = 1;
-    w.count = (int64_t *)take((size_t)w.tiles * 8);
-    w.offset = (int64_t *)take((size_t)w.tiles * 8);
-    w.prim_bytes = (size_t)(64u << 10) + (size_t)w.tiles * 8;
-    w.prim = take(w.prim_bytes);
-    w.bytes = off;
-    return w;
-}
-
 // ---- block vocabulary ------------------------------------------------------------------------------------------------
 // the sort's input: (hash, token index); slots behind the tokens hold the sentinel, which sorts last
 __global__ void vocab_sort_input(const uint64_t *__restrict__ hash, const int64_t *__restrict__ n_tokens, int64_t cap_tokens,
@@ -217,164 +194,19 @@ struct VocabWs {
 static VocabWs carve_vocab_ws(void *ws, int64_t cap_tokens)
 {
     VocabWs w;
-    size_t off = 0;
-    char *base = (char *)ws;
-    auto take = [&](size_t bytes) { void *q = base + off; off += align_up(bytes, 256); return q; };
+    WsCarver c{(char *)ws};
     const size_t n = (size_t)(cap_tokens > 0 ? cap_tokens : 1);
-    w.keys = (uint64_t *)take(n * 8);
-    w.keys_sorted = (uint64_t *)take(n * 8);
+    w.keys = c.take<uint64_t>(n);
+    w.keys_sorted = c.take<uint64_t>(n);
     w.ukeys = w.keys;                       // the unsorted hashes are dead once sorted
-    w.index = (uint32_t *)take(n * 4);
-    w.index_sorted = (uint32_t *)take(n * 4);
-    w.ucounts = (uint32_t *)take(n * 4);
-    w.run_start = (uint32_t *)take(n * 4);
-    w.n_unique = (int64_t *)take(256);
+    w.index = c.take<uint32_t>(n);
+    w.index_sorted = c.take<uint32_t>(n);
+    w.ucounts = c.take<uint32_t>(n);
+    w.run_start = c.take<uint32_t>(n);
+    w.n_unique = c.take<int64_t>(32);
     w.prim_bytes = (size_t)(16u << 20) + n * 24;
-    w.prim = take(w.prim_bytes);
-    w.bytes = off;
-    return w;
-}
-
-// ---- merge -----------------------------------------------------------------------------------------------------------
-// glove_cooc_stream.hip's merge (see there) with `where` as a second payload: summed counts, the smaller `where`
-constexpr int kTile = GLOVE_COOC_MERGE_TILE;
-constexpr int kVT = kTile / kBlock;
-static_assert(kVT * kBlock == kTile && kVT == 8, "a thread walks 8 merged positions");
-
-__global__ void vocab_merge_partition(const uint64_t *__restrict__ keys_a, const int64_t *__restrict__ n_a, int64_t cap_a,
-                                      const uint64_t *__restrict__ keys_b, const int64_t *__restrict__ n_b, int64_t cap_b,
-                                      int64_t tiles, int64_t *__restrict__ split_a, int64_t *__restrict__ split_b)
-{
-    const int64_t na = clamp_count(n_a, cap_a), nb = clamp_count(n_b, cap_b), L = na + nb;
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t <= tiles; t += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t diag = t * kTile < L ? t * kTile : L;
-        const int64_t ai = merge_path<int64_t>(keys_a, na, keys_b, nb, diag);
-        int64_t bi = diag - ai;
-        if (ai > 0 && bi < nb && keys_a[ai - 1] == keys_b[bi]) ++bi;
-        split_a[t] = ai;
-        split_b[t] = bi;
-    }
-}
-
-struct VocabTable { const uint64_t *keys; const int64_t *counts, *where, *n; int64_t cap; };
-
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void vocab_merge_tiles(
-    VocabTable a, VocabTable b, const int64_t *__restrict__ split_a, const int64_t *__restrict__ split_b,
-    int64_t *__restrict__ tile_count, const int64_t *__restrict__ tile_offset, uint64_t *__restrict__ keys_out,
-    int64_t *__restrict__ counts_out, int64_t *__restrict__ where_out, int64_t *__restrict__ n_out, int64_t cap_out)
-{
-    __shared__ __attribute__((aligned(16))) uint64_t sk[kTile + 2];
-    __shared__ __attribute__((aligned(16))) uint64_t sc[WRITE ? kTile + 2 : 2];
-    __shared__ __attribute__((aligned(16))) uint64_t sw[WRITE ? kTile + 2 : 2];
-    __shared__ int s_ai[kBlock + 1], s_bi[kBlock + 1];
-    __shared__ int s_wave[kBlock / 64];
-
-    const int64_t L = clamp_count(a.n, a.cap) + clamp_count(b.n, b.cap);
-    const int64_t tile = blockIdx.x;
-    const int tid = threadIdx.x;
-    if (WRITE && tile == (int64_t)gridDim.x - 1 && tid == 0) *n_out = tile_offset[tile] + tile_count[tile];
-    if (tile * kTile >= L) {              // beyond the merged length
-        if (!WRITE && tid == 0) tile_count[tile] = 0;
-        return;
-    }
-    const int64_t a0 = split_a[tile], b0 = split_b[tile];
-    const int nat = (int)(split_a[tile + 1] - a0), nbt = (int)(split_b[tile + 1] - b0), nt = nat + nbt;
-    load_words(a.keys + a0, nat, sk);
-    load_words(b.keys + b0, nbt, sk + nat);
-    if (WRITE) {
-        load_words((const uint64_t *)(a.counts + a0), nat, sc);
-        load_words((const uint64_t *)(b.counts + b0), nbt, sc + nat);
-        load_words((const uint64_t *)(a.where + a0), nat, sw);
-        load_words((const uint64_t *)(b.where + b0), nbt, sw + nat);
-    }
-    __syncthreads();
-
-    const uint64_t *A = sk, *B = sk + nat;
-    {
-        const int d = tid * kVT < nt ? tid * kVT : nt;
-        const int ai = merge_path<int>(A, nat, B, nbt, d);
-        int bi = d - ai;
-        if (ai > 0 && bi < nbt && A[ai - 1] == B[bi]) ++bi;
-        s_ai[tid] = ai;
-        s_bi[tid] = bi;
-        if (tid == 0) { s_ai[kBlock] = nat; s_bi[kBlock] = nbt; }
-    }
-    __syncthreads();
-    int i = s_ai[tid], j = s_bi[tid];
-    const int ie = s_ai[tid + 1], je = s_bi[tid + 1];
-
-    // the thread's stretch: an A entry takes its B twin with it; a B entry reached on its own has none
-    uint64_t ok[kVT + 1];
-    int64_t oc[kVT + 1], ow[kVT + 1];
-    int mine = 0;
-#pragma unroll
-    for (int s = 0; s < kVT + 1; ++s) {
-        const bool live = i < ie || j < je;
-        const bool has_a = i < ie, has_b = j < je;
-        const uint64_t ka = has_a ? A[i] : kNoKey, kb = has_b ? B[j] : kNoKey;
-        const bool take_a = has_a && (!has_b || ka <= kb);
-        const bool twin = take_a && has_b && ka == kb;
-        if (WRITE) {
-            const int64_t ca = has_a ? (int64_t)sc[i] : 0, cb = has_b ? (int64_t)sc[nat + j] : 0;
-            const int64_t wa = has_a ? (int64_t)sw[i] : 0, wb = has_b ? (int64_t)sw[nat + j] : 0;
-            ok[s] = take_a ? ka : kb;
-            oc[s] = take_a ? (twin ? ca + cb : ca) : cb;
-            ow[s] = take_a ? (twin && wb < wa ? wb : wa) : wb;
-        }
-        if (live) {
-            ++mine;
-            if (take_a) { ++i; if (twin) ++j; } else ++j;
-        }
-    }
-
-    int before, total;
-    block_exclusive_scan(mine, s_wave, before, total);      // its barrier: every thread is done reading sk / sc / sw
-    if (!WRITE) {
-        if (tid == 0) tile_count[tile] = total;
-        return;
-    }
-#pragma unroll
-    for (int s = 0; s < kVT + 1; ++s) {
-        if (s < mine) {
-            sk[before + s] = ok[s];
-            sc[before + s] = (uint64_t)oc[s];
-            sw[before + s] = (uint64_t)ow[s];
-        }
-    }
-    __syncthreads();
-    const int64_t off = tile_offset[tile];
-    const int64_t room = cap_out - off;
-    if (room <= 0) return;
-    const int n = room < total ? (int)room : total;
-    store_words(keys_out + off, n, sk);
-    store_words((uint64_t *)(counts_out + off), n, sc);
-    store_words((uint64_t *)(where_out + off), n, sw);
-}
-
-struct MergeWs {
-    int64_t *split_a, *split_b, *count, *offset;
-    void *prim;
-    size_t prim_bytes, bytes;
-    int64_t tiles;
-};
-
-// the layout of glove_cooc_stream.hip's carve_merge_ws
-static MergeWs carve_vocab_merge_ws(void *ws, int64_t cap_a, int64_t cap_b)
-{
-    MergeWs w;
-    size_t off = 0;
-    char *base = (char *)ws;
-    auto take = [&](size_t bytes) { void *q = base + off; off += align_up(bytes, 256); return q; };
-    w.tiles = (cap_a + cap_b + kTile - 1) / kTile;
-    if (w.tiles < 1) w.tiles = 1;
-    w.split_a = (int64_t *)take((size_t)(w.tiles + 1) * 8);
-    w.split_b = (int64_t *)take((size_t)(w.tiles + 1) * 8);
-    w.count = (int64_t *)take((size_t)w.tiles * 8);
-    w.offset = (int64_t *)take((size_t)w.tiles * 8);
-    w.prim_bytes = (size_t)(64u << 10) + (size_t)w.tiles * 8;
-    w.prim = take(w.prim_bytes);
-    w.bytes = off;
+    w.prim = c.take<char>(w.prim_bytes);
+    w.bytes = c.off;
     return w;
 }
 
@@ -406,24 +238,6 @@ __global__ void text_token_ids(const uint8_t *__restrict__ bytes, int64_t n_byte
     }
 }
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
-struct Range { const void *p; size_t n; };
-
-// does an output overlap an input or another output?
-template <size_t NO, size_t NI>
-static bool outputs_alias(const Range (&outs)[NO], const Range (&ins)[NI])
-{
-    for (size_t o = 0; o < NO; ++o) {
-        if (!outs[o].n) continue;
-        for (size_t i = 0; i < NI; ++i)
-            if (ins[i].n && overlap(outs[o].p, outs[o].n, ins[i].p, ins[i].n)) return true;
-        for (size_t q = o + 1; q < NO; ++q)
-            if (outs[q].n && overlap(outs[o].p, outs[o].n, outs[q].p, outs[q].n)) return true;
-    }
-    return false;
-}
-
 }  // namespace glove
 
 using namespace glove;
@@ -435,7 +249,7 @@ int glove_text_abi_version(void) { return GLOVE_TEXT_ABI_VERSION; }
 size_t glove_text_tokenize_workspace_bytes(int64_t n_bytes)
 {
     if (n_bytes < 0 || n_bytes > kMaxTextBytes) return 0;
-    return carve_tokenize_ws(nullptr, n_bytes).bytes;
+    return tile_counts_bytes(tiles_of(n_bytes, kTextTile));
 }
 
 int glove_text_tokenize_u8(const uint8_t *bytes, int64_t n_bytes, int32_t *start, int32_t *len, uint64_t *hash,
@@ -450,14 +264,14 @@ int glove_text_tokenize_u8(const uint8_t *bytes, int64_t n_bytes, int32_t *start
         return 0;
     }
     if (!bytes || (cap > 0 && (!start || !len || !hash))) return GLOVE_E_BADARG;
-    const TokenizeWs w = carve_tokenize_ws(ws, n_bytes);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
-    if (need > w.prim_bytes) return GLOVE_E_WORKSPACE;
+    WsCarver c{(char *)ws};
+    const TileCounts w = carve_tile_counts(c, tiles_of(n_bytes, kTextTile));
+    if (c.off > ws_bytes) return GLOVE_E_WORKSPACE;
+    size_t need;
+    if (const int rc = tile_scan_query(w, need, st)) return rc;
     const dim3 grid((unsigned int)w.tiles);
     hipLaunchKernelGGL(text_count_starts, grid, dim3(kBlock), 0, st, bytes, n_bytes, w.count, n_long);
-    HIP_TRY(rocprim::exclusive_scan(w.prim, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
+    HIP_TRY(tile_scan(w, w.prim, need, st));
     hipLaunchKernelGGL(text_emit_tokens, grid, dim3(kBlock), 0, st, bytes, n_bytes, w.count, w.offset, start, len, n_tokens, cap);
     // n_tokens lives on the device: the hashing pass is sized by the capacity (and by the most tokens the bytes can hold)
     const int64_t most = cap < (n_bytes + 1) / 2 ? cap : (n_bytes + 1) / 2;
@@ -505,44 +319,17 @@ int glove_text_block_vocab(const uint64_t *hash, const int32_t *start, const int
     return (int)hipGetLastError();
 }
 
-size_t glove_text_vocab_merge_workspace_bytes(int64_t cap_a, int64_t cap_b)
-{
-    if (cap_a < 0 || cap_b < 0 || cap_a > kMaxStateCap || cap_b > kMaxStateCap || cap_a + cap_b > kMaxStateCap) return 0;
-    return carve_vocab_merge_ws(nullptr, cap_a, cap_b).bytes;
-}
+size_t glove_text_vocab_merge_workspace_bytes(int64_t cap_a, int64_t cap_b) { return merge_workspace_bytes(cap_a, cap_b); }
 
 int glove_text_vocab_merge(const uint64_t *keys_a, const int64_t *counts_a, const int64_t *where_a, const int64_t *n_a,
                            int64_t cap_a, const uint64_t *keys_b, const int64_t *counts_b, const int64_t *where_b,
                            const int64_t *n_b, int64_t cap_b, uint64_t *keys_out, int64_t *counts_out, int64_t *where_out,
                            int64_t *n_out, int64_t cap_out, void *ws, size_t ws_bytes, void *stream)
 {
-    if (cap_a < 0 || cap_b < 0 || cap_out < 0 || cap_a > kMaxStateCap || cap_b > kMaxStateCap ||
-        cap_a + cap_b > kMaxStateCap || !n_a || !n_b || !n_out || !ws)
-        return GLOVE_E_BADARG;
-    if ((cap_a > 0 && (!keys_a || !counts_a || !where_a)) || (cap_b > 0 && (!keys_b || !counts_b || !where_b)) ||
-        (cap_out > 0 && (!keys_out || !counts_out || !where_out)))
-        return GLOVE_E_BADARG;
-    // the outputs are written while other tiles still read the inputs
-    const size_t ba = (size_t)cap_a * 8, bb = (size_t)cap_b * 8, bo = (size_t)cap_out * 8;
-    const Range ins[] = {{keys_a, ba}, {counts_a, ba}, {where_a, ba}, {keys_b, bb}, {counts_b, bb}, {where_b, bb}, {n_a, 8}, {n_b, 8}};
-    const Range outs[] = {{keys_out, bo}, {counts_out, bo}, {where_out, bo}, {n_out, 8}};
-    if (outputs_alias(outs, ins)) return GLOVE_E_BADARG;
-    const MergeWs w = carve_vocab_merge_ws(ws, cap_a, cap_b);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    size_t need = 0;
-    HIP_TRY(rocprim::exclusive_scan(nullptr, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
-    if (need > w.prim_bytes) return GLOVE_E_WORKSPACE;
-    const VocabTable a = {keys_a, counts_a, where_a, n_a, cap_a}, b = {keys_b, counts_b, where_b, n_b, cap_b};
-    hipLaunchKernelGGL(vocab_merge_partition, dim3(blocks_for(w.tiles + 1, kBlock)), dim3(kBlock), 0, st, keys_a, n_a, cap_a,
-                       keys_b, n_b, cap_b, w.tiles, w.split_a, w.split_b);
-    const dim3 grid((unsigned int)w.tiles);
-    hipLaunchKernelGGL(vocab_merge_tiles<false>, grid, dim3(kBlock), 0, st, a, b, w.split_a, w.split_b, w.count, w.offset,
-                       keys_out, counts_out, where_out, n_out, cap_out);
-    HIP_TRY(rocprim::exclusive_scan(w.prim, need, w.count, w.offset, (int64_t)0, (size_t)w.tiles, rocprim::plus<int64_t>(), st));
-    hipLaunchKernelGGL(vocab_merge_tiles<true>, grid, dim3(kBlock), 0, st, a, b, w.split_a, w.split_b, w.count, w.offset,
-                       keys_out, counts_out, where_out, n_out, cap_out);
-    return (int)hipGetLastError();
+    // summed counts, the smaller `where`: the word's first occurrence in the file
+    const MergeIn a = {keys_a, {counts_a, where_a}, n_a, cap_a}, b = {keys_b, {counts_b, where_b}, n_b, cap_b};
+    const MergeOut out = {keys_out, {counts_out, where_out}, n_out, cap_out};
+    return merge_tables(a, b, out, 2, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int glove_text_token_ids_i32(const uint8_t *bytes, int64_t n_bytes, const int32_t *start, const int32_t *len,

@@ -435,8 +435,6 @@ static FormatWs carve_format_ws(void *ws, int64_t n_rows)
     return w;
 }
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
-
 // one wave per item, kWaves to a workgroup
 static int wave_blocks(int64_t items) { return blocks_for(items, kWaves); }
 
