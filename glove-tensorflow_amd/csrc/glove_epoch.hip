@@ -552,12 +552,13 @@ int glove_masters_build(const int32_t *row, const int32_t *col, const float *w, 
 {
     if (n < 0 || V <= 0 || V_row < 0 || V_row > V || n >= (1ll << 31)) return GLOVE_E_BADARG;
     hipStream_t st = (hipStream_t)stream;
+    // (a refused call launches nothing: *mapped_out is zeroed once every argument has been accepted)
+    if (n > 0 && (!row || !col || !w || !y || !pairs_ok(row_major) || !pairs_ok(col_major) || !link || !ws)) return GLOVE_E_BADARG;
+    const MastersWs m = carve_masters(ws, n);
+    if (n > 0 && m.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
     if (mapped_out)
         if (hipError_t e = zero_words(mapped_out, 1, st)) return (int)e;
     if (n == 0) return 0;
-    if (!row || !col || !w || !y || !pairs_ok(row_major) || !pairs_ok(col_major) || !link || !ws) return GLOVE_E_BADARG;
-    const MastersWs m = carve_masters(ws, n);
-    if (m.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
     const int32_t Vr = V_row > 0 ? V_row : V;
     // bits of the ids of each order: [order][0 minor, 1 major]
     const int bits[2][2] = {{ceil_log2_64(V), ceil_log2_64(Vr)}, {ceil_log2_64(Vr), ceil_log2_64(V)}};

@@ -297,7 +297,8 @@ int glove_plan_build(const int32_t *row, const int32_t *col, const float *w, con
  *   glove_masters_build   the two master orders of the rank's nonzeros — row-major = sorted by (row id, col id, stream
  *                         index), col-major = sorted by (col id, row id, stream index) — and link[q] = the row-major position
  *                         of the pair at col-major position q.  Ids outside their table count as id 0 (the reference's
- *                         unknown-token id, estimator.py:26-28): *mapped_out (device int32, optional) = how many.
+ *                         unknown-token id, estimator.py:26-28): *mapped_out (device int32, optional) = how many
+ *                         (written by an accepted call only, n = 0 included: a refused call leaves it as it was).
  *   glove_epoch_deal      one epoch: a bijection seat() of [0, n) determined by the 128-bit key (the Feistel network of
  *                         glove_epoch.hip) gives the pair at row-major position p the seat seat(p), i.e. batch
  *                         seat(p) / B; a stable counting sort by batch number writes both orders so that batch k occupies
