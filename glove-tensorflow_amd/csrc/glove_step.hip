@@ -1022,24 +1022,16 @@ __global__ __launch_bounds__(kBlock) void apply_packed_kernel(
 // gradients AND the Adagrad applies — and a one-workgroup epilogue launch does the once-per-step scalars.  The reference's
 // default batch of 1,024 pairs (reference configs/app.ini:39-53) runs the two-launch form as two ramps, a kernel boundary and
 // four dependent memory round trips (record -> rows -> partial rows | id record -> partial + table rows -> rows), nothing in
-// them is bandwidth; here a chunk is record -> rows -> new row.
+// them is bandwidth; here a chunk is record -> rows -> new row (the chunk walk below, shared with the
+// one-launch Adam step).
 // What lets one launch both read every row as it was when the step began and update rows: both tables are twinned and
 // step-tagged (glove_tables.R_tag / C_tag).  tag[u] = 0, or (1 + step that wrote row u) << 1 | the copy it wrote.  During step t
 // a reader takes the copy the tag names unless the tag says "written in step t": then it takes the OTHER copy — the pre-step
 // row, which nobody touches during step t.  The writer (the one lane group that owns row u in this step) puts the new row into
 // the copy it did not read and then stores the tag.  A racing reader sees the old tag or the new one; either way it is led to
 // the pre-step row.  No barrier, no fence, no atomic (a device-scope fence costs 3 - 6 us on this chip: measured).
-//   * the tag is not waited for: the own row and the first trip's partner rows are requested in BOTH copies together with
-//     their tags (one round trip; the tables of this regime live in the caches) and the copy is chosen in registers;
-//   * an id's chunks are all done by the lane group that holds its FIRST chunk, one after the other (the groups that were
-//     dealt its other chunks skip them): per-chunk sums added in chunk order — for ids up to plan.heavy_chunks chunks the very
-//     order of the two-launch form's apply, bit for bit — then G = sum + activity-L2 term and Adagrad, expression for
-//     expression as AdagradApply.  No partial rows in memory.  (An id of many chunks is a long serial chain: the form is for
-//     batches whose ids have few chunks — GLOVE_STEP_AUTO takes it up to 2,048 pairs.)
-//   * every row-side workgroup leaves its loss partials; scalars_kernel (one workgroup, behind it on the stream) sums them in
-//     the fixed order of the two-launch form, updates the global bias, writes the loss and advances global_step — the one
-//     dependency between consecutive steps that needs all pairs, i.e. a grid-wide reduction: a kernel boundary is the
-//     cheapest one there is.
+// The tag is not waited for: the own row and the first trip's partner rows are requested in BOTH copies together with their
+// tags (one round trip; the tables of this regime live in the caches) and the copy is chosen in registers.
 // ------------------------------------------------------------------------------------------
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -1061,6 +1053,244 @@ __device__ inline uint32_t pre_step_copy(uint64_t tag, uint64_t t1 /* 1 + t */) 
 // step BEGAN, [8 + 4 b ..] the loss partials of its row-side workgroup b.
 constexpr int kChainHead = 8;
 
+// ------------------------------------------------------------------------------------------
+// The chunk walk of the one-launch kernels (tagged_step_kernel, tagged_adam_kernel), block by block.  An id's chunks are all
+// done by the lane group that holds its FIRST chunk, one after the other (the groups that were dealt its other chunks skip
+// them): per-chunk sums added in chunk order — for ids up to plan.heavy_chunks chunks the very order of the two-launch form's
+// apply, bit for bit — then G = sum + activity-L2 term and the optimizer, expression for expression as the apply launch.  No
+// partial rows in memory.  (An id of many chunks is a long serial chain: the forms are for batches whose ids have few chunks —
+// GLOVE_STEP_AUTO takes them up to 2,048 pairs.)  Every row-side workgroup leaves its loss partials in the step's chain record.
+// The kernels keep what is theirs: which copy of a row they read and write, the slots, the update.  Register arrays travel as
+// references of compile-time extent through forced inlining: nothing here may reach scratch.
+// ------------------------------------------------------------------------------------------
+constexpr int kWalkRecStride = 4 + 3 * kChunkMax + 4;       // dwords of a lane group's record in LDS
+template <int LPR> struct WalkPre { static constexpr int value = (1 + 3 * kChunkMax / 4 + LPR - 1) / LPR; };
+
+// The group's first record, requested before anything else: neither the number of chunks is waited for (a plan refilled on the
+// device keeps it in memory) nor the global bias (records exist up to the plan's capacity; one that lies behind the side's last
+// chunk is dropped unread).  (pre: a native vector type — an array of the struct uint4 went through scratch at four of them.)
+template <int LPR>
+__device__ __forceinline__ void record_request(u32x4 (&pre)[WalkPre<LPR>::value], const int32_t *crec, int capP, int cap_chunks, int jf, int lg)
+{
+    const uint4 *rp = reinterpret_cast<const uint4 *>(crec) + (size_t)(jf < cap_chunks ? jf : cap_chunks - 1) * rec_stride_q(capP);
+    const int rq0 = 1 + 3 * capP / 4;
+#pragma unroll
+    for (int x = 0; x < WalkPre<LPR>::value; ++x) {
+        const int f = lg + x * LPR;
+        pre[x] = reinterpret_cast<const u32x4 *>(rp)[rec_gq(f < rq0 ? f : 0)];
+    }
+}
+
+// Record j (descriptor + pair fields) in contiguous 16-B loads -> LDS as is: a round trip of its own
+template <int LPR>
+__device__ __forceinline__ void record_fetch(uint32_t *rec, const int32_t *crec, int j, int sq, int rq, int lg)
+{
+    const uint4 *rp = reinterpret_cast<const uint4 *>(crec) + (size_t)j * sq;
+    uint4 *lrec = reinterpret_cast<uint4 *>(rec);
+    for (int f = lg; f < rq; f += LPR) lrec[f] = rp[rec_gq(f)];
+}
+
+// ... the record a group begins with: the one requested at the kernel's start on its first round, from memory afterwards
+template <int LPR>
+__device__ __forceinline__ void record_first(uint32_t *rec, const u32x4 (&pre)[WalkPre<LPR>::value], bool requested, const int32_t *crec,
+                                             int j0, int sq, int rq, int lg)
+{
+    if (requested) {
+#pragma unroll
+        for (int x = 0; x < WalkPre<LPR>::value; ++x) {
+            const int f = lg + x * LPR;
+            if (f < rq) reinterpret_cast<u32x4 *>(rec)[f] = pre[x];
+        }
+    } else {
+        record_fetch<LPR>(rec, crec, j0, sq, rq, lg);
+    }
+}
+
+// {id, pairs, position of the id, first-chunk flag | chunks behind} (the same wave wrote it: LDS ops of one wave complete in order)
+__device__ __forceinline__ uint4 record_header(const uint32_t *rec) { return *reinterpret_cast<const uint4 *>(rec); }
+
+// Pairs q0 .. q0 + U - 1 of the record in LDS: partner row numbers (other_add: rows to the copy the step reads, where the whole
+// table has one), 2 w / B and y
+template <int U>
+__device__ __forceinline__ void unpack_pairs(const uint32_t *rec, int q0, uint32_t other_add, float inv_batch, int32_t (&col)[U],
+                                             float (&w2)[U], float (&yq)[U])
+{
+#pragma unroll
+    for (int a4 = 0; a4 < U; a4 += 4) {
+        const int rp0 = rec_pair(q0 + a4);
+        const uint4 pc = *reinterpret_cast<const uint4 *>(&rec[rp0]);
+        const uint4 pw = *reinterpret_cast<const uint4 *>(&rec[rp0 + kRecPad]);
+        const uint4 py = *reinterpret_cast<const uint4 *>(&rec[rp0 + 2 * kRecPad]);
+        col[a4] = (int32_t)(pc.x + other_add); col[a4 + 1] = (int32_t)(pc.y + other_add);
+        col[a4 + 2] = (int32_t)(pc.z + other_add); col[a4 + 3] = (int32_t)(pc.w + other_add);
+        const float sc2 = 2.0f * inv_batch;
+        w2[a4] = sc2 * __uint_as_float(pw.x); w2[a4 + 1] = sc2 * __uint_as_float(pw.y);
+        w2[a4 + 2] = sc2 * __uint_as_float(pw.z); w2[a4 + 3] = sc2 * __uint_as_float(pw.w);
+        yq[a4] = __uint_as_float(py.x); yq[a4 + 1] = __uint_as_float(py.y);
+        yq[a4 + 2] = __uint_as_float(py.z); yq[a4 + 3] = __uint_as_float(py.w);
+    }
+}
+
+// The partner rows of a trip whose row numbers are final, and their biases (lane 0 of the group; through the byte offset)
+template <int LPR, int NV, bool FULL, int U>
+__device__ __forceinline__ void gather_partners(f4 (&c)[U][NV], float (&bcv)[U], const float *other, const float *other_bias,
+                                                const int32_t (&col)[U], int d4, int lg)
+{
+#pragma unroll
+    for (int a = 0; a < U; ++a) {
+        load_row_fast<LPR, NV, FULL>(c[a], other, col[a], d4, lg);
+        bcv[a] = 0.f;
+        if (lg == 0) bcv[a] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(other_bias) + (uint32_t)col[a] * 4u);
+    }
+}
+
+// One trip: U pairs' dot products, summed over the lane group, through the head into the chunk's sums
+template <int LPR, int NV, int U>
+__device__ __forceinline__ void walk_trip(const f4 (&r)[NV], const f4 (&c)[U][NV], const float (&bcv)[U], const float (&w2)[U],
+                                          const float (&yq)[U], int q0, int n, float bg, int head, float inv_batch, float neg_factor,
+                                          f4 (&acc)[NV], float &se_c, float &cc_sum, float &bsq, float &ed)
+{
+    float dp[U], cc[U];
+#pragma unroll
+    for (int a = 0; a < U; ++a) {
+        dp[a] = 0.f; cc[a] = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) { dp[a] += dot4(r[k], c[a][k]); cc[a] += dot4(c[a][k], c[a][k]); }
+        dp[a] += bcv[a];
+    }
+#pragma unroll
+    for (int a = 0; a < U; ++a) dp[a] = dpp_add<0xB1>(dp[a]);
+#pragma unroll
+    for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x4E>(dp[a]);
+#pragma unroll
+    for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x141>(dp[a]);
+    if (LPR >= 16) {
+#pragma unroll
+        for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x140>(dp[a]);
+    }
+    if (LPR >= 32) {
+#pragma unroll
+        for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 16, 64);
+    }
+    if (LPR >= 64) {
+#pragma unroll
+        for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 32, 64);
+    }
+#pragma unroll
+    for (int a = 0; a < U; ++a) {
+        const float valid = (q0 + a < n) ? 1.0f : 0.f;
+        float e;
+        if (head == GLOVE_HEAD_REGRESSION) {
+            const float diff = (dp[a] + bg) - yq[a];
+            e = w2[a] * diff;
+            ed += e * diff;
+        } else {
+            const float p = dp[a] + bg;
+            const float en = expf(-fabsf(p));
+            const float s = (p >= 0.f ? 1.0f : en) / (1.0f + en);
+            const float lse = log1pf(en);
+            const float wn = 2.0f * inv_batch * neg_factor * valid * yq[a];
+            e = 0.5f * (w2[a] * (s - 1.0f) + wn * s);
+            ed += w2[a] * (fmaxf(-p, 0.f) + lse) + wn * (fmaxf(p, 0.f) + lse);
+        }
+#pragma unroll
+        for (int k = 0; k < NV; ++k) acc[k] += e * c[a][k];
+        se_c += e;
+        cc_sum += valid * cc[a];
+        bsq += valid * bcv[a] * bcv[a];
+    }
+}
+
+// A chunk is done: the row side's loss partials, and the id's sums in chunk order (the first chunk's taken as they are, like
+// the apply launch's traversal)
+template <int NV>
+__device__ __forceinline__ void chunk_close(bool is_row, bool first, int n, int lg, const f4 (&r)[NV], float own_b, const f4 (&acc)[NV],
+                                            float se_c, float cc_sum, float bsq, float ed, float (&part)[kPartials], f4 (&G)[NV], float &Gb)
+{
+    if (is_row) {
+        float rr = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) rr += dot4(r[k], r[k]);
+        part[1] += cc_sum + (float)n * rr;
+        if (lg == 0) {
+            part[0] += ed;
+            part[2] += bsq + (float)n * own_b * own_b;
+            part[3] += se_c;
+        }
+    }
+    if (first) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) G[k] = acc[k];
+        Gb = se_c;
+    } else {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) G[k] += acc[k];
+        Gb += se_c;
+    }
+}
+
+// G = summed gradient + activity-L2 term (for_each_id, expression for expression)
+template <int NV>
+__device__ __forceinline__ void add_activity_l2(f4 (&G)[NV], float &Gb, const f4 (&r)[NV], float bval, int pairs, const StepConsts &kc)
+{
+    const float cnt = (float)pairs;
+    const float kcn = kc.kappa * cnt;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) G[k] += kcn * r[k];
+    Gb += kc.kappa_b * cnt * bval;
+}
+
+// The workgroup's loss partials into the step's chain record (row side only)
+__device__ __forceinline__ void walk_partials_store(bool is_row, float (&part)[kPartials], float inv_batch, float *blockpart)
+{
+    if (is_row) {
+        part[0] *= 0.5f / inv_batch;        // sum e diff = 2 inv_batch sum w diff^2
+        block_partials_store(part, blockpart);
+    }
+}
+
+// The global bias of THIS step.  The one thing a step needs of ALL pairs of the step before is sum e (the global bias'
+// gradient): a grid-wide reduction.  Instead of a launch (or a device-scope fence: 3 - 6 us) between the steps of a chain, every
+// workgroup of step i derives the bias itself — from the bias step i - 1 began with (and its slots: Adagrad's accumulator, or
+// Adam's m and v with the step t - 1 that lr_t needs) and the loss partials its row-side workgroups left (prev), summed in the
+// fixed order of the two-launch form: same bits in every workgroup — and leaves what it began with in a record of its own
+// (mine), which nobody of this launch reads.  A chain's first step takes the bias from the tables' scalars.
+template <int OPT>
+__device__ __forceinline__ float chain_bias(const float *__restrict__ prev, int prev_blocks, const float *__restrict__ scalars,
+                                            float *__restrict__ mine, const StepConsts &kc, float b1, float b2, double ln_beta1,
+                                            double ln_beta2, int64_t t)
+{
+    constexpr bool kAdam = OPT == GLOVE_OPT_ADAM;
+    __shared__ float s_g[kAdam ? 3 : 2];
+    if (prev) {
+        float tot[kPartials];
+        sum_blockpart(prev + kChainHead, prev_blocks, tot);
+        if (threadIdx.x == 0) {
+            const float g0 = prev[0];
+            const float dg = tot[3] + 2.0f * kc.m * kc.l2 * g0;
+            float gn = g0, s1 = prev[1];
+            if constexpr (kAdam) {
+                float s2 = prev[2];
+                adam_elem(gn, s1, s2, dg, adam_lr_t(kc.lr, ln_beta1, ln_beta2, t - 1), b1, b2, kc.eps);
+                s_g[2] = s2;
+            } else {
+                adagrad_elem(gn, s1, dg, kc.lr, kc.eps);
+            }
+            s_g[0] = gn; s_g[1] = s1;
+        }
+    } else if (threadIdx.x == 0) {
+        s_g[0] = scalars[0]; s_g[1] = scalars[1];
+        if constexpr (kAdam) s_g[2] = scalars[2];
+    }
+    __syncthreads();
+    const float g = s_g[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        mine[0] = g; mine[1] = s_g[1];
+        if constexpr (kAdam) mine[2] = s_g[2];
+    }
+    return g;
+}
+
 template <int LPR, int NV, bool FULL>
 __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
     const int32_t *__restrict__ counts, OneSide rowside, OneSide colside, int row_blocks, const float *__restrict__ scalars,
@@ -1069,29 +1299,15 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
 {
     constexpr int GPB = kBlock / LPR;
     constexpr int U = PassUnroll<NV>::value;
-    constexpr int kRecStride = 4 + 3 * kChunkMax + 4;
-    __shared__ __attribute__((aligned(16))) uint32_t fld_raw[GPB * kRecStride];
-    uint32_t *rec = fld_raw + (threadIdx.x / LPR) * kRecStride;
+    __shared__ __attribute__((aligned(16))) uint32_t fld_raw[GPB * kWalkRecStride];
+    uint32_t *rec = fld_raw + (threadIdx.x / LPR) * kWalkRecStride;
     const int lg = threadIdx.x % LPR, grp = threadIdx.x / LPR;
     const bool is_row = (int)blockIdx.x < row_blocks;
     const OneSide &sd = is_row ? rowside : colside;
     const int bid = is_row ? blockIdx.x : blockIdx.x - row_blocks;
     const int nblk = is_row ? row_blocks : gridDim.x - row_blocks;
-    // the number of chunks is not waited for either (a plan refilled on the device keeps it in memory), nor the bias below: the
-    // group's first record is requested before anything else (records exist up to the plan's capacity; one that lies behind
-    // the side's last chunk is dropped unread)
-    constexpr int kPre = (1 + 3 * kChunkMax / 4 + LPR - 1) / LPR;
-    u32x4 pre[kPre];       // (a native vector type: an array of the struct uint4 went through scratch at kPre = 4)
-    {
-        const int jf = bid * GPB + grp;
-        const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)(jf < sd.cap_chunks ? jf : sd.cap_chunks - 1) * rec_stride_q(sd.capP);
-        const int rq0 = 1 + 3 * sd.capP / 4;
-#pragma unroll
-        for (int x = 0; x < kPre; ++x) {
-            const int f = lg + x * LPR;
-            pre[x] = reinterpret_cast<const u32x4 *>(rp)[rec_gq(f < rq0 ? f : 0)];
-        }
-    }
+    u32x4 pre[WalkPre<LPR>::value];
+    record_request<LPR>(pre, sd.crec, sd.capP, sd.cap_chunks, bid * GPB + grp, lg);
     const int n_chunks = sd.n_host >= 0 ? sd.n_host : counts[sd.count_index];
     // global_step stands still during a chain (its last launch's epilogue advances it): this is step *step + chain_i
     const uint64_t t1 = (uint64_t)(*step) + (uint64_t)chain_i + 1ull;
@@ -1099,46 +1315,13 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
     const int capP = sd.capP;
     const int rq = 1 + 3 * capP / 4;
     const int sq = rec_stride_q(capP);
-    // ---- the global bias of THIS step.  The one thing a step needs of ALL pairs of the step before is sum e (the global bias'
-    // gradient): a grid-wide reduction.  Instead of a launch (or a device-scope fence: 3 - 6 us) between the steps, every
-    // workgroup of step i derives the bias itself — from the bias step i - 1 began with and the loss partials its row-side
-    // workgroups left (prev), summed in the fixed order of the two-launch form: same bits in every workgroup — and leaves what
-    // it began with, and its own partials, in a record of its own (mine), which nobody of this launch reads.
-    __shared__ float s_g[2];
-    if (prev) {
-        float tot[kPartials];
-        sum_blockpart(prev + kChainHead, prev_blocks, tot);
-        if (threadIdx.x == 0) {
-            const float g0 = prev[0];
-            const float dg = tot[3] + 2.0f * kc.m * kc.l2 * g0;
-            float gn = g0, Ag = prev[1];
-            adagrad_elem(gn, Ag, dg, kc.lr, kc.eps);
-            s_g[0] = gn; s_g[1] = Ag;
-        }
-    } else if (threadIdx.x == 0) {
-        s_g[0] = scalars[0]; s_g[1] = scalars[1];
-    }
-    __syncthreads();
-    const float g = s_g[0];
-    if (blockIdx.x == 0 && threadIdx.x == 0) { mine[0] = g; mine[1] = s_g[1]; }
+    const float g = chain_bias<GLOVE_OPT_ADAGRAD>(prev, prev_blocks, scalars, mine, kc, 0.f, 0.f, 0.0, 0.0, 0);
     float *blockpart = mine + kChainHead;
 
     for (int j0 = bid * GPB + grp; j0 < n_chunks; j0 += nblk * GPB) {
-        // ---- round trip 1: the record (descriptor + pair fields) in contiguous 16-B loads -> LDS as is
-        {
-            uint4 *lrec = reinterpret_cast<uint4 *>(rec);
-            if (j0 == bid * GPB + grp) {                        // (requested at the kernel's start)
-#pragma unroll
-                for (int x = 0; x < kPre; ++x) {
-                    const int f = lg + x * LPR;
-                    if (f < rq) reinterpret_cast<u32x4 *>(lrec)[f] = pre[x];
-                }
-            } else {
-                const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)j0 * sq;
-                for (int f = lg; f < rq; f += LPR) lrec[f] = rp[rec_gq(f)];
-            }
-        }
-        uint4 hdr = *reinterpret_cast<const uint4 *>(rec);      // same wave wrote it: LDS ops of one wave complete in order
+        // ---- round trip 1: the record
+        record_first<LPR>(rec, pre, j0 == bid * GPB + grp, sd.crec, j0, sq, rq, lg);
+        uint4 hdr = record_header(rec);
         if (!(hdr.w >> 31)) continue;                           // not the first chunk of its id: the group that holds the first one does it
         const int32_t u = (int32_t)hdr.x;
         const int chunks = 1 + (int)(hdr.w & 0x7fffffffu);
@@ -1156,12 +1339,9 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
         uint32_t own_copy = 0;
         int pairs = 0;
         for (int ch = 0; ch < chunks; ++ch) {
-            const int j = j0 + ch;
-            if (ch > 0) {                                       // the id's next chunk: its record (a round trip of its own)
-                const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)j * sq;
-                uint4 *lrec = reinterpret_cast<uint4 *>(rec);
-                for (int f = lg; f < rq; f += LPR) lrec[f] = rp[rec_gq(f)];
-                hdr = *reinterpret_cast<const uint4 *>(rec);
+            if (ch > 0) {                                       // the id's next chunk
+                record_fetch<LPR>(rec, sd.crec, j0 + ch, sq, rq, lg);
+                hdr = record_header(rec);
             }
             const int n = (int)hdr.y;
             pairs += n;
@@ -1180,19 +1360,7 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
             for (int q0 = 0; q0 < n; q0 += U) {
                 int32_t col[U];
                 float w2[U], yq[U];
-#pragma unroll
-                for (int a4 = 0; a4 < U; a4 += 4) {
-                    const int rp0 = rec_pair(q0 + a4);
-                    const uint4 pc = *reinterpret_cast<const uint4 *>(&rec[rp0]);
-                    const uint4 pw = *reinterpret_cast<const uint4 *>(&rec[rp0 + kRecPad]);
-                    const uint4 py = *reinterpret_cast<const uint4 *>(&rec[rp0 + 2 * kRecPad]);
-                    col[a4] = (int32_t)pc.x; col[a4 + 1] = (int32_t)pc.y; col[a4 + 2] = (int32_t)pc.z; col[a4 + 3] = (int32_t)pc.w;
-                    const float sc2 = 2.0f * inv_batch;
-                    w2[a4] = sc2 * __uint_as_float(pw.x); w2[a4 + 1] = sc2 * __uint_as_float(pw.y);
-                    w2[a4 + 2] = sc2 * __uint_as_float(pw.z); w2[a4 + 3] = sc2 * __uint_as_float(pw.w);
-                    yq[a4] = __uint_as_float(py.x); yq[a4 + 1] = __uint_as_float(py.y);
-                    yq[a4 + 2] = __uint_as_float(py.z); yq[a4 + 3] = __uint_as_float(py.w);
-                }
+                unpack_pairs<U>(rec, q0, 0u, inv_batch, col, w2, yq);
                 f4 c[U][NV];
                 float bcv[U];
                 if (q0 == 0) {
@@ -1232,97 +1400,20 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
                         if (t < n && t >= U) rec[rec_pair(t)] += pre_step_copy(ptag[x], t1) ? (uint32_t)sd.other_twin : 0u;
                     }
                 } else {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) {
-                        load_row_fast<LPR, NV, FULL>(c[a], sd.other, col[a], d4, lg);
-                        bcv[a] = 0.f;
-                        if (lg == 0) bcv[a] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(sd.other_bias) + (uint32_t)col[a] * 4u);
-                    }
+                    gather_partners<LPR, NV, FULL, U>(c, bcv, sd.other, sd.other_bias, col, d4, lg);
                 }
-                float dp[U], cc[U];
-#pragma unroll
-                for (int a = 0; a < U; ++a) {
-                    dp[a] = 0.f; cc[a] = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) { dp[a] += dot4(r[k], c[a][k]); cc[a] += dot4(c[a][k], c[a][k]); }
-                    dp[a] += bcv[a];
-                }
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0xB1>(dp[a]);
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x4E>(dp[a]);
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x141>(dp[a]);
-                if (LPR >= 16) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x140>(dp[a]);
-                }
-                if (LPR >= 32) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 16, 64);
-                }
-                if (LPR >= 64) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 32, 64);
-                }
-#pragma unroll
-                for (int a = 0; a < U; ++a) {
-                    const float valid = (q0 + a < n) ? 1.0f : 0.f;
-                    float e;
-                    if (head == GLOVE_HEAD_REGRESSION) {
-                        const float diff = (dp[a] + bg) - yq[a];
-                        e = w2[a] * diff;
-                        ed += e * diff;
-                    } else {
-                        const float p = dp[a] + bg;
-                        const float en = expf(-fabsf(p));
-                        const float s = (p >= 0.f ? 1.0f : en) / (1.0f + en);
-                        const float lse = log1pf(en);
-                        const float wn = 2.0f * inv_batch * neg_factor * valid * yq[a];
-                        e = 0.5f * (w2[a] * (s - 1.0f) + wn * s);
-                        ed += w2[a] * (fmaxf(-p, 0.f) + lse) + wn * (fmaxf(p, 0.f) + lse);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) acc[k] += e * c[a][k];
-                    se_c += e;
-                    cc_sum += valid * cc[a];
-                    bsq += valid * bcv[a] * bcv[a];
-                }
+                walk_trip<LPR, NV, U>(r, c, bcv, w2, yq, q0, n, bg, head, inv_batch, neg_factor, acc, se_c, cc_sum, bsq, ed);
             }
-            if (is_row) {
-                float rr = 0.f;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) rr += dot4(r[k], r[k]);
-                part[1] += cc_sum + (float)n * rr;
-                if (lg == 0) {
-                    part[0] += ed;
-                    part[2] += bsq + (float)n * own_b * own_b;
-                    part[3] += se_c;
-                }
-            }
-            // the id's sums: chunk sums in chunk order (the first one taken as it is, like the apply launch's traversal)
-            if (ch == 0) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) G[k] = acc[k];
-                Gb = se_c;
-            } else {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) G[k] += acc[k];
-                Gb += se_c;
-            }
+            chunk_close<NV>(is_row, ch == 0, n, lg, r, own_b, acc, se_c, cc_sum, bsq, ed, part, G, Gb);
         }
-        // ---- G = summed gradient + activity-L2 term, then Adagrad (for_each_id + AdagradApply, expression for expression)
+        // ---- Adagrad (AdagradApply, expression for expression) into the copy nobody reads during this step, then the tag
         {
             float bval = own_b;
-            const float cnt = (float)pairs;
-            const float kcn = kc.kappa * cnt;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) G[k] += kcn * r[k];
-            Gb += kc.kappa_b * cnt * bval;
+            add_activity_l2<NV>(G, Gb, r, bval, pairs, kc);
 #pragma unroll
             for (int k = 0; k < NV; ++k) adagrad_vec(r[k], A[k], G[k], kc.lr, kc.eps);
             store_row<LPR, NV>(sd.S1, (size_t)u, d4, lg, A);
-            const int32_t new_at = u + (own_copy ? 0 : sd.own_twin);      // the copy nobody reads during this step
+            const int32_t new_at = u + (own_copy ? 0 : sd.own_twin);
             store_row<LPR, NV>(sd.own, (size_t)new_at, d4, lg, r);
             if (lg == 0) {
                 adagrad_elem(bval, Ab, Gb, kc.lr, kc.eps);
@@ -1332,20 +1423,16 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_step_kernel(
             }
         }
     }
-    if (is_row) {
-        part[0] *= 0.5f / inv_batch;        // sum e diff = 2 inv_batch sum w diff^2
-        block_partials_store(part, blockpart);
-    }
+    walk_partials_store(is_row, part, inv_batch, blockpart);
 }
 
 // ------------------------------------------------------------------------------------------
 // Keras-legacy Adam in ONE launch per step (the reference's default optimizer at its default batch: configs/app.ini:39-53),
 // on twinned tables.  The legacy optimizer's sparse path rewrites EVERY row every step (m *= b1, v *= b2, var -= lr_t
 // m / (sqrt(v) + eps) over the whole table, a11), so the twin needs no tags: a step reads copy c of both tables and writes
-// copy 1 - c of both, all rows — the batch's rows by the lane group that holds the first chunk of the id (gradient, then
-// Adam, as in the tagged Adagrad step), every other row by a sweep that finds the batch's ids in the plan's bitmaps
-// (glove_plan.r_mark / c_mark) and leaves them alone.  scalars[3] says which copy is current between chains.  The global bias
-// travels through chain records like the tagged Adagrad step's ([0] bias, [1] m, [2] v as the step began).
+// copy 1 - c of both, all rows — the batch's rows by the chunk walk above (gradient, then Adam), every other row by a sweep
+// that finds the batch's ids in the plan's bitmaps (glove_plan.r_mark / c_mark) and leaves them alone.  scalars[3] says which
+// copy is current between chains.  The global bias travels through chain records ([0] bias, [1] m, [2] v as the step began).
 // ------------------------------------------------------------------------------------------
 // ... in tagged_adam_kernel: four where the registers allow (d = 64: 10.8 -> 10.2 us per step; six spill: 14.2)
 constexpr int tagged_sweep_rows(int nv) { return nv <= 2 ? 4 : 2; }
@@ -1422,67 +1509,26 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_adam_kernel(
         return;
     }
     constexpr int U = PassUnroll<NV>::value;
-    constexpr int kRecStride = 4 + 3 * kChunkMax + 4;
-    __shared__ __attribute__((aligned(16))) uint32_t fld_raw[GPB * kRecStride];
-    uint32_t *rec = fld_raw + (threadIdx.x / LPR) * kRecStride;
+    __shared__ __attribute__((aligned(16))) uint32_t fld_raw[GPB * kWalkRecStride];
+    uint32_t *rec = fld_raw + (threadIdx.x / LPR) * kWalkRecStride;
     const bool is_row = (int)blockIdx.x < row_blocks;
     const AdamSide &sd = is_row ? rowside : colside;
     const int bid = is_row ? blockIdx.x : blockIdx.x - row_blocks;
     const int nblk = is_row ? row_blocks : chunk_blocks - row_blocks;
-    // the group's first record is requested before anything else (as in tagged_step_kernel)
-    constexpr int kPre = (1 + 3 * kChunkMax / 4 + LPR - 1) / LPR;
-    u32x4 pre[kPre];       // (a native vector type: an array of the struct uint4 went through scratch at kPre = 4)
-    {
-        const int jf = bid * GPB + grp;
-        const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)(jf < sd.cap_chunks ? jf : sd.cap_chunks - 1) * rec_stride_q(sd.capP);
-        const int rq0 = 1 + 3 * sd.capP / 4;
-#pragma unroll
-        for (int x = 0; x < kPre; ++x) {
-            const int f = lg + x * LPR;
-            pre[x] = reinterpret_cast<const u32x4 *>(rp)[rec_gq(f < rq0 ? f : 0)];
-        }
-    }
+    u32x4 pre[WalkPre<LPR>::value];
+    record_request<LPR>(pre, sd.crec, sd.capP, sd.cap_chunks, bid * GPB + grp, lg);
     const int n_chunks = sd.n_host >= 0 ? sd.n_host : counts[sd.count_index];
     float part[kPartials] = {0.f, 0.f, 0.f, 0.f};
     const int capP = sd.capP;
     const int rq = 1 + 3 * capP / 4;
     const int sq = rec_stride_q(capP);
-    // ---- the global bias of THIS step: derived by every workgroup from the record the step before left (tagged_step_kernel)
-    __shared__ float s_g[3];
-    if (prev) {
-        float tot[kPartials];
-        sum_blockpart(prev + kChainHead, prev_blocks, tot);
-        if (threadIdx.x == 0) {
-            const float g0 = prev[0];
-            const float dg = tot[3] + 2.0f * kc.m * kc.l2 * g0;
-            float gn = g0, Mg = prev[1], Vg = prev[2];
-            adam_elem(gn, Mg, Vg, dg, adam_lr_t(kc.lr, ln_beta1, ln_beta2, t - 1), b1, b2, kc.eps);
-            s_g[0] = gn; s_g[1] = Mg; s_g[2] = Vg;
-        }
-    } else if (threadIdx.x == 0) {
-        s_g[0] = scalars[0]; s_g[1] = scalars[1]; s_g[2] = scalars[2];
-    }
-    __syncthreads();
-    const float g = s_g[0];
-    if (blockIdx.x == 0 && threadIdx.x == 0) { mine[0] = g; mine[1] = s_g[1]; mine[2] = s_g[2]; }
+    const float g = chain_bias<GLOVE_OPT_ADAM>(prev, prev_blocks, scalars, mine, kc, b1, b2, ln_beta1, ln_beta2, t);
     float *blockpart = mine + kChainHead;
     const uint32_t other_add = cur ? (uint32_t)sd.other_twin : 0u;
 
     for (int j0 = bid * GPB + grp; j0 < n_chunks; j0 += nblk * GPB) {
-        {
-            uint4 *lrec = reinterpret_cast<uint4 *>(rec);
-            if (j0 == bid * GPB + grp) {
-#pragma unroll
-                for (int x = 0; x < kPre; ++x) {
-                    const int f = lg + x * LPR;
-                    if (f < rq) reinterpret_cast<u32x4 *>(lrec)[f] = pre[x];
-                }
-            } else {
-                const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)j0 * sq;
-                for (int f = lg; f < rq; f += LPR) lrec[f] = rp[rec_gq(f)];
-            }
-        }
-        uint4 hdr = *reinterpret_cast<const uint4 *>(rec);
+        record_first<LPR>(rec, pre, j0 == bid * GPB + grp, sd.crec, j0, sq, rq, lg);
+        uint4 hdr = record_header(rec);
         if (!(hdr.w >> 31)) continue;                           // the group that holds the id's first chunk does the whole id
         const int32_t u = (int32_t)hdr.x;
         const int chunks = 1 + (int)(hdr.w & 0x7fffffffu);
@@ -1499,12 +1545,9 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_adam_kernel(
         float Gb = 0.f;
         int pairs = 0;
         for (int ch = 0; ch < chunks; ++ch) {
-            const int j = j0 + ch;
             if (ch > 0) {
-                const uint4 *rp = reinterpret_cast<const uint4 *>(sd.crec) + (size_t)j * sq;
-                uint4 *lrec = reinterpret_cast<uint4 *>(rec);
-                for (int f = lg; f < rq; f += LPR) lrec[f] = rp[rec_gq(f)];
-                hdr = *reinterpret_cast<const uint4 *>(rec);
+                record_fetch<LPR>(rec, sd.crec, j0 + ch, sq, rq, lg);
+                hdr = record_header(rec);
             }
             const int n = (int)hdr.y;
             pairs += n;
@@ -1515,106 +1558,17 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_adam_kernel(
             for (int q0 = 0; q0 < n; q0 += U) {
                 int32_t col[U];
                 float w2[U], yq[U];
-#pragma unroll
-                for (int a4 = 0; a4 < U; a4 += 4) {
-                    const int rp0 = rec_pair(q0 + a4);
-                    const uint4 pc = *reinterpret_cast<const uint4 *>(&rec[rp0]);
-                    const uint4 pw = *reinterpret_cast<const uint4 *>(&rec[rp0 + kRecPad]);
-                    const uint4 py = *reinterpret_cast<const uint4 *>(&rec[rp0 + 2 * kRecPad]);
-                    col[a4] = (int32_t)(pc.x + other_add); col[a4 + 1] = (int32_t)(pc.y + other_add);
-                    col[a4 + 2] = (int32_t)(pc.z + other_add); col[a4 + 3] = (int32_t)(pc.w + other_add);
-                    const float sc2 = 2.0f * inv_batch;
-                    w2[a4] = sc2 * __uint_as_float(pw.x); w2[a4 + 1] = sc2 * __uint_as_float(pw.y);
-                    w2[a4 + 2] = sc2 * __uint_as_float(pw.z); w2[a4 + 3] = sc2 * __uint_as_float(pw.w);
-                    yq[a4] = __uint_as_float(py.x); yq[a4 + 1] = __uint_as_float(py.y);
-                    yq[a4 + 2] = __uint_as_float(py.z); yq[a4 + 3] = __uint_as_float(py.w);
-                }
+                unpack_pairs<U>(rec, q0, other_add, inv_batch, col, w2, yq);
                 f4 c[U][NV];
                 float bcv[U];
-#pragma unroll
-                for (int a = 0; a < U; ++a) {
-                    load_row_fast<LPR, NV, FULL>(c[a], sd.other, col[a], d4, lg);
-                    bcv[a] = 0.f;
-                    if (lg == 0) bcv[a] = *reinterpret_cast<const float *>(reinterpret_cast<const char *>(sd.other_bias) + (uint32_t)col[a] * 4u);
-                }
-                float dp[U], cc[U];
-#pragma unroll
-                for (int a = 0; a < U; ++a) {
-                    dp[a] = 0.f; cc[a] = 0.f;
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) { dp[a] += dot4(r[k], c[a][k]); cc[a] += dot4(c[a][k], c[a][k]); }
-                    dp[a] += bcv[a];
-                }
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0xB1>(dp[a]);
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x4E>(dp[a]);
-#pragma unroll
-                for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x141>(dp[a]);
-                if (LPR >= 16) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] = dpp_add<0x140>(dp[a]);
-                }
-                if (LPR >= 32) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 16, 64);
-                }
-                if (LPR >= 64) {
-#pragma unroll
-                    for (int a = 0; a < U; ++a) dp[a] += __shfl_xor(dp[a], 32, 64);
-                }
-#pragma unroll
-                for (int a = 0; a < U; ++a) {
-                    const float valid = (q0 + a < n) ? 1.0f : 0.f;
-                    float e;
-                    if (head == GLOVE_HEAD_REGRESSION) {
-                        const float diff = (dp[a] + bg) - yq[a];
-                        e = w2[a] * diff;
-                        ed += e * diff;
-                    } else {
-                        const float p = dp[a] + bg;
-                        const float en = expf(-fabsf(p));
-                        const float s = (p >= 0.f ? 1.0f : en) / (1.0f + en);
-                        const float lse = log1pf(en);
-                        const float wn = 2.0f * inv_batch * neg_factor * valid * yq[a];
-                        e = 0.5f * (w2[a] * (s - 1.0f) + wn * s);
-                        ed += w2[a] * (fmaxf(-p, 0.f) + lse) + wn * (fmaxf(p, 0.f) + lse);
-                    }
-#pragma unroll
-                    for (int k = 0; k < NV; ++k) acc[k] += e * c[a][k];
-                    se_c += e;
-                    cc_sum += valid * cc[a];
-                    bsq += valid * bcv[a] * bcv[a];
-                }
+                gather_partners<LPR, NV, FULL, U>(c, bcv, sd.other, sd.other_bias, col, d4, lg);
+                walk_trip<LPR, NV, U>(r, c, bcv, w2, yq, q0, n, bg, head, inv_batch, neg_factor, acc, se_c, cc_sum, bsq, ed);
             }
-            if (is_row) {
-                float rr = 0.f;
-#pragma unroll
-                for (int k = 0; k < NV; ++k) rr += dot4(r[k], r[k]);
-                part[1] += cc_sum + (float)n * rr;
-                if (lg == 0) {
-                    part[0] += ed;
-                    part[2] += bsq + (float)n * own_b * own_b;
-                    part[3] += se_c;
-                }
-            }
-            if (ch == 0) {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) G[k] = acc[k];
-                Gb = se_c;
-            } else {
-#pragma unroll
-                for (int k = 0; k < NV; ++k) G[k] += acc[k];
-                Gb += se_c;
-            }
+            chunk_close<NV>(is_row, ch == 0, n, lg, r, own_b, acc, se_c, cc_sum, bsq, ed, part, G, Gb);
         }
         {
             float bval = own_b;
-            const float cnt = (float)pairs;
-            const float kcn = kc.kappa * cnt;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) G[k] += kcn * r[k];
-            Gb += kc.kappa_b * cnt * bval;
+            add_activity_l2<NV>(G, Gb, r, bval, pairs, kc);
 #pragma unroll
             for (int k = 0; k < NV; ++k) adam_vec(r[k], M[k], Vv[k], G[k], lr_t, b1, b2, kc.eps);
             store_row<LPR, NV>(sd.S1, (size_t)u, d4, lg, M);
@@ -1629,10 +1583,7 @@ __global__ __launch_bounds__(kBlock, NV <= 2 ? 2 : 1) void tagged_adam_kernel(
             }
         }
     }
-    if (is_row) {
-        part[0] *= 0.5f / inv_batch;
-        block_partials_store(part, blockpart);
-    }
+    walk_partials_store(is_row, part, inv_batch, blockpart);
 }
 
 // The end of a chain of n one-launch steps: the last step's loss partials -> the loss scalars and the global bias the NEXT step

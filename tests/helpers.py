@@ -65,6 +65,35 @@ def oracle_tables(V, d, optimizer, seed=1):
     return t.astype(np.float64)
 
 
+def _tagged(t):
+    """Device tables of the oracle's state, twinned and step-tagged: what the one-launch Adagrad step runs on."""
+    from trainer.hip_api import DeviceTables
+    dt = tables_from_oracle(t, DeviceTables)
+    dt.enable_tags()
+    assert dt.R_tag is not None
+    return dt
+
+
+def _mid_run(V, d, seed=5, step=17):
+    """Adam tables in a mid-run state: m, v of every row non-zero, so that the sweep's decay shows."""
+    t = oracle_tables(V, d, "Adam")
+    rng = np.random.default_rng(seed)
+    for n in ("R", "C", "br", "bc"):
+        setattr(t, "M_" + n, rng.normal(0, 1e-3, getattr(t, n).shape).astype(np.float32).astype(np.float64))
+        setattr(t, "V_" + n, (rng.uniform(0, 1e-5, getattr(t, n).shape)).astype(np.float32).astype(np.float64))
+    t.step = step
+    return t
+
+
+def _twinned(t):
+    """Device tables of the oracle's state with both tables twinned: what the one-launch Adam step runs on."""
+    from trainer.hip_api import DeviceTables
+    dt = tables_from_oracle(t, DeviceTables)
+    dt.enable_tags()
+    assert dt.R_tag is not None and dt._R.shape[0] == 2 * dt.V_row
+    return dt
+
+
 def assert_tables_close(dt, t, rtol=1e-5, atol=1e-6):
     dm = dt.d_model
     got = lambda x: (x[:, :dm] if x.dim() == 2 else x).cpu().numpy()

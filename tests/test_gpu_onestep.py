@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import glove_ref as ref
-from helpers import assert_tables_close, make_batch, oracle_tables, tables_from_oracle, to_dev
+from helpers import _tagged, assert_tables_close, make_batch, oracle_tables, tables_from_oracle, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -18,14 +18,6 @@ def _hyper(hp, B, form):
     from trainer.hip_api import make_hyper
     return make_hyper(l2_reg=hp.l2_reg, reg_mult=hp.reg_mult, learning_rate=hp.learning_rate, epsilon=hp.epsilon, batch_size=B,
                       head=hp.head, neg_factor=hp.neg_factor, step_form=form)
-
-
-def _tagged(t):
-    from trainer.hip_api import DeviceTables
-    dt = tables_from_oracle(t, DeviceTables)
-    dt.enable_tags()
-    assert dt.R_tag is not None
-    return dt
 
 
 CASES = [(1024, 10000, 64, 16), (1024, 300, 64, 16), (4096, 12000, 64, 16), (700, 50, 16, 2), (3000, 40, 16, 5), (2048, 500, 128, 32),

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import glove_ref as ref
-from helpers import assert_tables_close, make_batch, oracle_tables, tables_from_oracle, to_dev
+from helpers import _mid_run, _twinned, assert_tables_close, make_batch, oracle_tables, tables_from_oracle, to_dev
 
 pytestmark = pytest.mark.gpu
 
@@ -20,25 +20,6 @@ def _hyper(hp, B, form=0):
     from trainer.hip_api import make_hyper
     return make_hyper(l2_reg=hp.l2_reg, reg_mult=hp.reg_mult, learning_rate=hp.learning_rate, epsilon=hp.epsilon, batch_size=B,
                       head=hp.head, neg_factor=hp.neg_factor, step_form=form)
-
-
-def _mid_run(V, d, seed=5, step=17):
-    """Adam tables in a mid-run state: m, v of every row non-zero, so that the sweep's decay shows."""
-    t = oracle_tables(V, d, "Adam")
-    rng = np.random.default_rng(seed)
-    for n in ("R", "C", "br", "bc"):
-        setattr(t, "M_" + n, rng.normal(0, 1e-3, getattr(t, n).shape).astype(np.float32).astype(np.float64))
-        setattr(t, "V_" + n, (rng.uniform(0, 1e-5, getattr(t, n).shape)).astype(np.float32).astype(np.float64))
-    t.step = step
-    return t
-
-
-def _twinned(t):
-    from trainer.hip_api import DeviceTables
-    dt = tables_from_oracle(t, DeviceTables)
-    dt.enable_tags()
-    assert dt.R_tag is not None and dt._R.shape[0] == 2 * dt.V_row
-    return dt
 
 
 CASES = [(1024, 10000, 64, 16), (1024, 2000, 50, 16), (512, 1000, 300, 32), (2048, 3000, 128, 32), (1, 10, 64, 16), (20, 50, 16, 2),
