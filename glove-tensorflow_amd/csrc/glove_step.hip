@@ -2062,6 +2062,19 @@ static StepConsts make_consts(const glove_tables *t, const glove_hyper *h)
     return k;
 }
 
+// Opens the call of an entry point: the arguments every step-path call shares are checked here, once, and nowhere behind it.
+// `carved`: the workspace holds the layout of carve_step_ws and must have its size (the one-launch chains keep their own records
+// there instead: launch_tagged_chain)
+static int open_call(StepCall &c, const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
+                     void *stream, bool carved = true)
+{
+    if (int rc = check_common(p, t, h, ws)) return rc;
+    const int d4 = t->d / 4;
+    c = StepCall{p, t, h, ws, ws_bytes, (hipStream_t)stream, carve_step_ws(ws, p->B, p->cap_chunks, t->d), d4, pick_row_shape(d4),
+                 pick_pass_shape(d4), sides_of(h), make_consts(t, h)};
+    return carved && c.w.bytes > ws_bytes ? GLOVE_E_WORKSPACE : 0;
+}
+
 // The optimizer's own hyper-parameters as the apply kernels take them; the logs of the betas in fp64 (adam_lr_t)
 struct OptHyper { OptConsts o; float b1, b2; double ln_b1, ln_b2; };
 static OptHyper opt_consts(const glove_hyper *h)
@@ -2157,6 +2170,27 @@ static SideBufs side_bufs(const glove_plan *p, const StepWs &w, const glove_tabl
     s.ver = nullptr;            // set by the twin step alone: every other caller sees a canonical table
     s.twin = 0;
     return s;
+}
+
+// What a launch over the batch's ids (for_each_id) takes: the ids of `sides`, behind passes that fused pre_r / pre_c (the twin
+// step's caller has seen R_ver); the grid, and the workgroups of the row-side pass whose loss partials the scalar duty sums
+struct IdLaunch { IdWork wk; SideBufs rs, cs; int nb, nb_row; };
+static IdLaunch id_launch(const StepCall &c, int sides, int pre_r = kFuseNone, int pre_c = kFuseNone)
+{
+    IdLaunch l{id_work(c.p), side_bufs(c.p, c.w, c.t, true), side_bufs(c.p, c.w, c.t, false), apply_blocks(c.p, c.shape), 0};
+    const bool fused = pre_r != kFuseNone || pre_c != kFuseNone, pack = pre_r == kFusePack || pre_c == kFusePack;
+    l.wk.sides = sides;
+    l.wk.pre_r = pre_r;
+    l.wk.pre_c = pre_c;
+    l.wk.per = fused ? fuse_per(c.p, c.pass.lpr) : 1;
+    l.wk.gpb = fused && !pack && solid_groups(c.p) ? kBlock / c.pass.lpr : 0;      // (as launch_passes: the packing passes are never solid)
+    // (the first launch of the step; behind the packing row pass its grid too — or folded by glove_rowside_step_adagrad_f32: any count reads them)
+    l.nb_row = fused ? fusepass_blocks(c.p, c.pass.lpr, l.wk.per, true) : rowpass_blocks(c.p, c.pass.lpr);
+    if (pre_r == kFuseTwin) {
+        l.rs.ver = c.t->R_ver;
+        l.rs.twin = v_row(c.t);
+    }
+    return l;
 }
 
 // One side of a one-launch step: S = OneSide (Adagrad: the step tags) or AdamSide (the second slot, the bitmap of the batch's ids)
@@ -2265,45 +2299,69 @@ static PassSide pass_side(const glove_plan *p, const glove_tables *t, const Step
     return sd;
 }
 
-// which: 1 = row side, 2 = col side, 3 = both in one launch
-static int launch_passes(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                         void *stream, int which, float *mark_rows = nullptr, float *mark_cols = nullptr,
-                         bool want_e = false, int fuse_r = kFuseNone, int fuse_c = kFuseNone, bool twin = false,
-                         float *packed = nullptr, bool list_tail = false)
+static inline bool has_slot1(const glove_tables *t) { return t->s1_R && t->s1_C && t->s1_br && t->s1_bc; }
+
+// What a launch of the passes does beyond the plain pass of its sides; a call site names only that
+struct PassOpts {
+    int which;                                          // 1 = row side, 2 = col side, 3 = both in one launch
+    float *mark_rows = nullptr, *mark_cols = nullptr;   // the batch's ids marked (the Adam steps' sweeps leave those rows alone)
+    bool want_e = false;                                // the diagnostic row pass: e by pair position
+    int fuse_r = kFuseNone, fuse_c = kFuseNone;
+    bool twin = false;                                  // follow the version bytes of a twinned row table
+    float *packed = nullptr;                            // the list kFusePack writes
+    bool list_tail = false;                             // the twin form's col-side launch lists the apply launch's ids
+    explicit PassOpts(int which_) : which(which_) {}
+    PassOpts &marks(float *rows, float *cols) { mark_rows = rows; mark_cols = cols; return *this; }
+    PassOpts &with_e() { want_e = true; return *this; }
+    PassOpts &fuse(int r, int c) { fuse_r = r; fuse_c = c; return *this; }
+    PassOpts &on_twin(bool tail = false) { twin = true; list_tail = tail; return *this; }
+    PassOpts &packing(float *list) { packed = list; return fuse(which & 1 ? kFusePack : kFuseNone, which & 2 ? kFusePack : kFuseNone); }
+    bool packs() const { return fuse_r == kFusePack || fuse_c == kFusePack; }
+    // (the diagnostic row pass stores e by pair position, which the records do not carry: it reads the plain arrays)
+    bool records(const glove_plan *p) const { return p->r_crec != nullptr && p->c_crec != nullptr && !want_e; }
+};
+
+// Everything a launch of the passes can refuse, launch_passes' first act: an entry point asks before its own first launch
+static int check_passes(const StepCall &c, const PassOpts &o)
 {
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    const bool fuse = fuse_r != kFuseNone || fuse_c != kFuseNone || twin;
-    if ((twin || fuse_r == kFuseTwin) && !t->R_ver) return GLOVE_E_BADARG;
-    if (fuse_c == kFuseTwin) return GLOVE_E_BADARG;          // only the row table has a twin
-    const bool applies = twin || (fuse_r != kFuseNone && fuse_r != kFusePack) || (fuse_c != kFuseNone && fuse_c != kFusePack);
-    if (applies && (!t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc)) return GLOVE_E_BADARG;
+    const glove_plan *p = c.p;
+    const glove_tables *t = c.t;
+    if ((o.twin || o.fuse_r == kFuseTwin) && !t->R_ver) return GLOVE_E_BADARG;
+    if (o.fuse_c == kFuseTwin) return GLOVE_E_BADARG;          // only the row table has a twin
+    const bool applies = o.twin || (o.fuse_r != kFuseNone && o.fuse_r != kFusePack) || (o.fuse_c != kFuseNone && o.fuse_c != kFusePack);
+    if (applies && !has_slot1(t)) return GLOVE_E_BADARG;
     // in place is only legal for a side whose table no concurrent chunk gathers from: one side per launch
-    if ((fuse_r == kFuseInPlace && (which & 2)) || (fuse_c == kFuseInPlace && (which & 1))) return GLOVE_E_BADARG;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_pass_shape(d4);
+    if ((o.fuse_r == kFuseInPlace && (o.which & 2)) || (o.fuse_c == kFuseInPlace && (o.which & 1))) return GLOVE_E_BADARG;
+    // the packing build neither applies nor reads plain arrays: records, and no other fuse mode beside it
+    if (o.packs() && (!o.packed || p->host_counts[1] < 0 || !p->r_crec || !p->c_crec || o.want_e || applies)) return GLOVE_E_BADARG;
+    if (o.list_tail && (!o.twin || o.which != 2 || o.fuse_c != kFuseInPlace || !c.w.work || c.sides != 3)) return GLOVE_E_BADARG;
+    if (!o.records(p) && p->B > 0 && !p->r_partner) return GLOVE_E_BADARG;     // (the diagnostic pass needs pair arrays)
+    return 0;
+}
+
+static int launch_passes(const StepCall &c, const PassOpts &o)
+{
+    if (int rc = check_passes(c, o)) return rc;
+    const glove_plan *p = c.p;
+    const glove_tables *t = c.t;
+    const RowShape shape = c.pass;
+    const int which = o.which, fuse_r = o.fuse_r, fuse_c = o.fuse_c;
+    const bool twin = o.twin, pack = o.packs(), fuse = fuse_r != kFuseNone || fuse_c != kFuseNone || twin;
     const int per = fuse ? fuse_per(p, shape.lpr) : 1;
     const int row_blocks = !(which & 1) ? 0 : fuse ? fusepass_blocks(p, shape.lpr, per, true) : rowpass_blocks(p, shape.lpr);
     const int nb = row_blocks + (!(which & 2) ? 0 : fuse ? fusepass_blocks(p, shape.lpr, per, false) : rowpass_blocks(p, shape.lpr));
-    PassSide rs = pass_side(p, t, w, true, want_e, fuse_r, twin), cs = pass_side(p, t, w, false, false, fuse_c, twin);
-    rs.mark = mark_rows;
-    cs.mark = mark_cols;
-    const bool pack = fuse_r == kFusePack || fuse_c == kFusePack;
+    PassSide rs = pass_side(p, t, c.w, true, o.want_e, fuse_r, twin), cs = pass_side(p, t, c.w, false, false, fuse_c, twin);
+    rs.mark = o.mark_rows;
+    cs.mark = o.mark_cols;
     if (pack) {
-        // the packing build neither applies nor reads plain arrays: records, and no other fuse mode beside it
-        if (!packed || p->host_counts[1] < 0 || !p->r_crec || !p->c_crec || want_e || applies) return GLOVE_E_BADARG;
-        rs.own_out = cs.own_out = packed;
+        rs.own_out = cs.own_out = o.packed;
         rs.own_twin = 1;                                                  // behind the header
         cs.own_twin = 1 + (fuse_r == kFusePack ? p->host_counts[1] : 0);  // and behind the row side's ids when both sides pack
     }
-    const StepConsts kc = make_consts(t, h);
-    hipStream_t st = (hipStream_t)stream;
     // the twin form's col-side launch: behind the pass, the workgroups that list the ids the apply launch has to visit
     ListTail tail{p->counts, p->r_uniq_rec, p->c_uniq_rec, p->host_counts[1], p->host_counts[3], p->heavy_chunks, per, -1};
     int nb_launch = nb;
-    if (list_tail) {
-        if (!twin || which != 2 || fuse_c != kFuseInPlace || !w.work || sides_of(h) != 3) return GLOVE_E_BADARG;
+    if (o.list_tail) {
         const int64_t ids = tail.nu_r_host >= 0 && tail.nu_c_host >= 0 ? (int64_t)tail.nu_r_host + tail.nu_c_host : 2 * (int64_t)p->cap_uniq;
         tail.first_block = nb;
         nb_launch = nb + (int)((ids + kBlock - 1) / kBlock);
@@ -2312,12 +2370,9 @@ static int launch_passes(const glove_plan *p, const glove_tables *t, const glove
     // the twin form's streaming cache policy: row tables beyond the Infinity Cache's reach (on the 61 MB table of V = 50 k, d = 300
     // it costs 3 - 8 %: the next launch finds the finished rows in the caches there)
     const bool streaming = (size_t)v_row(t) * (size_t)t->d * 4 >= ((size_t)128 << 20);
-    // (the diagnostic row pass stores e by pair position, which the records do not carry: it reads the plain arrays)
-    const bool rec = p->r_crec != nullptr && p->c_crec != nullptr && !want_e;
-    if (!rec && p->B > 0 && !p->r_partner) return GLOVE_E_BADARG;     // (the diagnostic pass needs pair arrays)
     // sidepass_kernel's builds live in four objects, by shape.  The wide shapes of one float4 per lane stay here: their code is the
     // one-unit build's only in a module that also holds the per-id apply functors (profiles/r11_step_units_resource_usage.txt)
-    const PassLaunch a{p, t, h, rs, cs, w, kc, tail, shape, d4, per, row_blocks, nb, nb_launch, which, twin, solid, streaming, rec, pack, fuse, st};
+    const PassLaunch a{c, rs, cs, tail, per, row_blocks, nb, nb_launch, which, twin, solid, streaming, o.records(p), pack, fuse};
     int rc;
     if (shape.lpr == 8) rc = launch_passes_lpr8(a);                                 // <8, 1>, <8, 2>
     else if (shape.nv == 1) rc = launch_pass_shapes<32, 1, 64, 1>(a);
@@ -2327,78 +2382,67 @@ static int launch_passes(const glove_plan *p, const glove_tables *t, const glove
     return (int)hipGetLastError();
 }
 
+// One launch of the passes as an entry point: refused before anything is launched, a twinned table brought home first
+static int passes_on_plain_table(const StepCall &c, const PassOpts &o)
+{
+    if (int rc = check_passes(c, o)) return rc;
+    if (int rc = plain_table(c.t, c.st)) return rc;
+    return launch_passes(c, o);
+}
+
 int glove_passes_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                      void *stream)
 {
-    if (int rc = plain_table(t, stream)) return rc;
-    return launch_passes(p, t, h, ws, ws_bytes, stream, 3);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    return passes_on_plain_table(c, PassOpts(3));
 }
 
 int glove_rowpass_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                       void *stream)
 {
-    if (int rc = plain_table(t, stream)) return rc;
-    return launch_passes(p, t, h, ws, ws_bytes, stream, 1, nullptr, nullptr, true);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    return passes_on_plain_table(c, PassOpts(1).with_e());
 }
 
 int glove_colpass_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                       void *stream)
 {
-    if (int rc = plain_table(t, stream)) return rc;
-    return launch_passes(p, t, h, ws, ws_bytes, stream, 2);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    return passes_on_plain_table(c, PassOpts(2));
 }
 
-static int launch_apply_adagrad(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws,
-                                size_t ws_bytes, float *loss_out, void *stream, int pre_r, int pre_c, bool listed = false)
+// (its caller has seen the Adagrad slots — has_slot1 —, and R_ver where pre_r is kFuseTwin)
+static int launch_apply_adagrad(const StepCall &c, float *loss_out, int pre_r, int pre_c, bool listed = false)
 {
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    if (!t->s1_R || !t->s1_C || !t->s1_br || !t->s1_bc) return GLOVE_E_BADARG;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    IdWork wk = id_work(p);
-    wk.sides = sides_of(h);
-    wk.pre_r = pre_r;
-    wk.pre_c = pre_c;
-    const bool fused = pre_r != kFuseNone || pre_c != kFuseNone;
-    wk.per = fused ? fuse_per(p, pick_pass_shape(d4).lpr) : 1;
-    wk.gpb = fused && solid_groups(p) ? kBlock / pick_pass_shape(d4).lpr : 0;
-    const int nb = apply_blocks(p, shape);
-    // workgroups of the row-side pass, whose loss partials the scalar duty sums (the first launch of the step)
-    const int nb_row = fused ? fusepass_blocks(p, pick_pass_shape(d4).lpr, wk.per, true) : rowpass_blocks(p, pick_pass_shape(d4).lpr);
-    const StepConsts k = make_consts(t, h);
-    SideBufs rs = side_bufs(p, w, t, true);
-    const SideBufs cs = side_bufs(p, w, t, false);
-    if (pre_r == kFuseTwin) {
-        if (!t->R_ver) return GLOVE_E_BADARG;
-        rs.ver = t->R_ver;
-        rs.twin = v_row(t);
-    }
-    hipStream_t st = (hipStream_t)stream;
+    IdLaunch l = id_launch(c, c.sides, pre_r, pre_c);
+    IdWork &wk = l.wk;
+    int32_t *const work = c.w.work;
     const bool short_list = (pre_r == kFuseTwin && pre_c == kFuseInPlace && wk.sides == 3) ||
                             (pre_r == kFuseInPlace && wk.sides == 1);        // glove_rowside_step_adagrad_f32
     if (listed) {
         // the col-side launch drew the list (ListTail); the finished row ids' version flips are this launch's (for_each_id)
-        if (!(pre_r == kFuseTwin && pre_c == kFuseInPlace && wk.sides == 3) || !w.work) return GLOVE_E_BADARG;
-        wk.work = w.work;
+        if (!(pre_r == kFuseTwin && pre_c == kFuseInPlace && wk.sides == 3) || !work) return GLOVE_E_BADARG;
+        wk.work = work;
         wk.flips = 1;
-    } else if (short_list && w.work) {
+    } else if (short_list && work) {
         // sort the ids out first (triage_kernel, a thread per id): the launch below then walks the list of those that
         // still need it.  Only where that list is short — the twin form, whose finished ids need a version flip at most
         // (V = 400 k, d = 300: apply 62 -> 12 us + 5 us of triage), and the in-place row side of the sharded forms,
         // whose finished ids need nothing.  Behind the slot form every row id still needs its
         // copy, nearly all ids go onto the list and its one counter becomes the bottleneck (V = 2 M: 51 us of triage)
-        wk.work = w.work;
+        wk.work = work;
         // (a plan refilled on the device: a thread per id the arrays can hold, the kernel reads the counts)
-        const int64_t ids = wk.nu_r_host >= 0 && wk.nu_c_host >= 0 ? (int64_t)wk.nu_r_host + wk.nu_c_host : 2 * (int64_t)p->cap_uniq;
+        const int64_t ids = wk.nu_r_host >= 0 && wk.nu_c_host >= 0 ? (int64_t)wk.nu_r_host + wk.nu_c_host : 2 * (int64_t)c.p->cap_uniq;
         const int nbt = (int)((ids + kBlock - 1) / kBlock);
-        if (nbt > 0) hipLaunchKernelGGL(triage_kernel, dim3(nbt), dim3(kBlock), 0, st, wk, rs, cs, w.work);
+        if (nbt > 0) hipLaunchKernelGGL(triage_kernel, dim3(nbt), dim3(kBlock), 0, c.st, wk, l.rs, l.cs, work);
     }
-#define CALL(LPR, NV)                                                                                          \
-    hipLaunchKernelGGL((apply_adagrad_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, d4,        \
-                       k, t->scalars, w.blockpart, nb_row, loss_out)
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+#define CALL(LPR, NV)                                                                                             \
+    hipLaunchKernelGGL((apply_adagrad_kernel<LPR, NV>), dim3(l.nb), dim3(kBlock), 0, c.st, wk, l.rs, l.cs, c.d4, \
+                       c.k, c.t->scalars, c.w.blockpart, l.nb_row, loss_out)
+    GLOVE_DISPATCH_ROW_SHAPE(c.shape, CALL);
 #undef CALL
     return (int)hipGetLastError();
 }
@@ -2406,33 +2450,24 @@ static int launch_apply_adagrad(const glove_plan *p, const glove_tables *t, cons
 int glove_apply_adagrad_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws,
                             size_t ws_bytes, float *loss_out, void *stream)
 {
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (!has_slot1(t)) return GLOVE_E_BADARG;
     if (int rc = plain_table(t, stream)) return rc;
-    return launch_apply_adagrad(p, t, h, ws, ws_bytes, loss_out, stream, kFuseNone, kFuseNone);
+    return launch_apply_adagrad(c, loss_out, kFuseNone, kFuseNone);
 }
 
-static int launch_dense_grad(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                             float *G_flat, void *stream)
+// (its caller has seen G_flat)
+static int launch_dense_grad(const StepCall &c, float *G_flat)
 {
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    if (!G_flat) return GLOVE_E_BADARG;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    IdWork wk = id_work(p);
-    wk.sides = sides_of(h);
-    const int nb = apply_blocks(p, shape);
-    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
-    const StepConsts k = make_consts(t, h);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    const GradLayout L = grad_layout(v_row(t), t->V, t->d);
+    const IdLaunch l = id_launch(c, c.sides);
+    const GradLayout L = grad_layout(v_row(c.t), c.t->V, c.t->d);
     float *G_R = G_flat + L.G_R, *G_C = G_flat + L.G_C, *G_br = G_flat + L.G_br, *G_bc = G_flat + L.G_bc,
           *tail = G_flat + L.tail;
-    hipStream_t st = (hipStream_t)stream;
-#define CALL(LPR, NV)                                                                                       \
-    hipLaunchKernelGGL((dense_grad_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, d4,        \
-                       k, G_R, G_C, G_br, G_bc, tail, w.blockpart, nb_row)
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+#define CALL(LPR, NV)                                                                                                  \
+    hipLaunchKernelGGL((dense_grad_kernel<LPR, NV>), dim3(l.nb), dim3(kBlock), 0, c.st, l.wk, l.rs, l.cs, c.d4,       \
+                       c.k, G_R, G_C, G_br, G_bc, tail, c.w.blockpart, l.nb_row)
+    GLOVE_DISPATCH_ROW_SHAPE(c.shape, CALL);
 #undef CALL
     return (int)hipGetLastError();
 }
@@ -2440,13 +2475,19 @@ static int launch_dense_grad(const glove_plan *p, const glove_tables *t, const g
 int glove_dense_grad_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                          float *G_flat, void *stream)
 {
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (!G_flat) return GLOVE_E_BADARG;
     if (int rc = plain_table(t, stream)) return rc;
-    return launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream);
+    return launch_dense_grad(c, G_flat);
 }
 
-static int dense_common(const glove_tables *t, const glove_hyper *h, float *G_flat, bool adam, DenseSegs &segs,
-                        float *&tail, int &nbx, int &sides)
+// A dense sweep's launch: the four segments of the tables and of G_flat, the grid, whether the scalar work is its own
+struct DenseSweep { DenseSegs segs; float *tail; int nbx, do_scalars; };
+
+static int dense_common(const glove_tables *t, const glove_hyper *h, float *G_flat, bool adam, DenseSweep &sw)
 {
+    DenseSegs &segs = sw.segs;
     if (!t || !h || !G_flat || t->V <= 0 || t->d <= 0 || (t->d % 4) != 0 || t->d_model < 0 || t->d_model > t->d)
         return GLOVE_E_BADARG;
     if (!t->R || !t->C || !t->br || !t->bc || !t->scalars || !t->step) return GLOVE_E_BADARG;
@@ -2454,85 +2495,75 @@ static int dense_common(const glove_tables *t, const glove_hyper *h, float *G_fl
     if (adam && (!t->s2_R || !t->s2_C || !t->s2_br || !t->s2_bc)) return GLOVE_E_BADARG;
     const int32_t Vr = v_row(t);
     const GradLayout L = grad_layout(Vr, t->V, t->d);
-    tail = G_flat + L.tail;
-    sides = sides_of(h);
+    sw.tail = G_flat + L.tail;
+    const int sides = sides_of(h);
+    sw.do_scalars = (sides & 2) ? 1 : 0;
     // segment order = grid.y: 0 R, 1 C (float4 bodies), 2 br, 3 bc (scalar); a side that is not covered gets n = 0
     const int64_t nr = (sides & 1) ? 1 : 0, nc = (sides & 2) ? 1 : 0;
     segs.s[0] = {t->R, t->s1_R, t->s2_R, G_flat + L.G_R, nr * Vr * t->d};
     segs.s[1] = {t->C, t->s1_C, t->s2_C, G_flat + L.G_C, nc * t->V * t->d};
     segs.s[2] = {t->br, t->s1_br, t->s2_br, G_flat + L.G_br, nr * Vr};
     segs.s[3] = {t->bc, t->s1_bc, t->s2_bc, G_flat + L.G_bc, nc * t->V};
-    nbx = blocks_for((int64_t)(Vr > t->V ? Vr : t->V) * t->d / 4, kBlock);
+    sw.nbx = blocks_for((int64_t)(Vr > t->V ? Vr : t->V) * t->d / 4, kBlock);
     return 0;
 }
 
 int glove_dense_adagrad_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
 {
-    DenseSegs segs; float *tail; int nbx, sides;
+    DenseSweep sw;
     if (h && h->optimizer == GLOVE_OPT_ROWWISE_ADAGRAD) return GLOVE_E_BADARG;      // its table slots are float[rows]: nothing to sweep
+    if (int rc = dense_common(t, h, G_flat, false, sw)) return rc;
     if (int rc = plain_table(t, stream)) return rc;
-    if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
-    const StepConsts k = make_consts(t, h);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(dense_adagrad_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, t->scalars, tail, loss_out,
-                       (sides & 2) ? 1 : 0);
+    hipLaunchKernelGGL(dense_adagrad_kernel, dim3(sw.nbx, 4), dim3(kBlock), 0, (hipStream_t)stream, sw.segs, make_consts(t, h), t->scalars,
+                       sw.tail, loss_out, sw.do_scalars);
     return (int)hipGetLastError();
 }
 
-int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
+// The dense sweep of glove_hyper.optimizer over G_flat: Adam's, or RMSprop's — the other dense-decay optimizer of the Keras set:
+// its whole rms slot decays every step, entries with a gradient move.  What it refuses, and its launch.
+static int check_dense_sweep(const glove_tables *t, const glove_hyper *h, float *G_flat, DenseSweep &sw)
 {
-    DenseSegs segs; float *tail; int nbx, sides;
     // touched rows only: no dense sweep (RowWiseAdagrad's table slots are not even shaped like the tables a sweep walks)
     if (h && (h->optimizer == GLOVE_OPT_LAZYADAM || h->optimizer == GLOVE_OPT_ROWWISE_ADAGRAD)) return GLOVE_E_BADARG;
-    if (int rc = plain_table(t, stream)) return rc;
-    if (h && h->optimizer == GLOVE_OPT_RMSPROP) {
-        // the other dense-decay optimizer of the Keras set: its whole rms slot decays every step, entries with a gradient move —
-        // the sweep of glove_step_sparse_f32, here on a G_flat that holds the ranks' summed gradients (data-parallel step)
-        if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
-        if (!(h->rho > 0.f && h->rho < 1.f)) return GLOVE_E_BADARG;
-        hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, (hipStream_t)stream, segs, make_consts(t, h), h->rho,
-                           t->scalars, tail, loss_out, (sides & 2) ? 1 : 0);
-        return (int)hipGetLastError();
-    }
-    if (int rc = dense_common(t, h, G_flat, true, segs, tail, nbx, sides)) return rc;
-    if (!(h->beta1 > 0.0 && h->beta1 < 1.0 && h->beta2 > 0.0 && h->beta2 < 1.0)) return GLOVE_E_BADARG;
+    const bool rmsprop = h && h->optimizer == GLOVE_OPT_RMSPROP;
+    if (int rc = dense_common(t, h, G_flat, !rmsprop, sw)) return rc;
+    if (rmsprop) return h->rho > 0.f && h->rho < 1.f ? 0 : GLOVE_E_BADARG;
+    return h->beta1 > 0.0 && h->beta1 < 1.0 && h->beta2 > 0.0 && h->beta2 < 1.0 ? 0 : GLOVE_E_BADARG;
+}
+
+static int launch_dense_sweep(const glove_tables *t, const glove_hyper *h, const DenseSweep &sw, float *loss_out, hipStream_t st)
+{
     const StepConsts k = make_consts(t, h);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(dense_adam_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, (float)h->beta1, (float)h->beta2,
-                       log((double)(float)h->beta1), log((double)(float)h->beta2), t->step, t->scalars, tail, loss_out, (sides & 2) ? 1 : 0);
+    if (h->optimizer == GLOVE_OPT_RMSPROP)
+        hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(sw.nbx, 4), dim3(kBlock), 0, st, sw.segs, k, h->rho, t->scalars, sw.tail, loss_out,
+                           sw.do_scalars);
+    else
+        hipLaunchKernelGGL(dense_adam_kernel, dim3(sw.nbx, 4), dim3(kBlock), 0, st, sw.segs, k, (float)h->beta1, (float)h->beta2,
+                           log((double)(float)h->beta1), log((double)(float)h->beta2), t->step, t->scalars, sw.tail, loss_out, sw.do_scalars);
     return (int)hipGetLastError();
+}
+
+// (on a G_flat that holds the ranks' summed gradients: the data-parallel step)
+int glove_dense_adam_f32(const glove_tables *t, const glove_hyper *h, float *G_flat, float *loss_out, void *stream)
+{
+    DenseSweep sw;
+    if (int rc = check_dense_sweep(t, h, G_flat, sw)) return rc;
+    if (int rc = plain_table(t, stream)) return rc;
+    return launch_dense_sweep(t, h, sw, loss_out, (hipStream_t)stream);
+}
+
+// The passes of `which`, their summed gradients into G_flat, the dense sweep over it: refused as a whole before the first launch
+static int dense_step(const StepCall &c, int which, float *G_flat, float *loss_out)
+{
+    DenseSweep sw;
+    if (int rc = check_dense_sweep(c.t, c.h, G_flat, sw)) return rc;
+    if (int rc = plain_table(c.t, c.st)) return rc;
+    if (int rc = launch_passes(c, PassOpts(which))) return rc;
+    if (int rc = launch_dense_grad(c, G_flat)) return rc;
+    return launch_dense_sweep(c.t, c.h, sw, loss_out, c.st);
 }
 
 static_assert(GLOVE_PACKED_ENTRY_FLOATS(0) == (size_t)kPackExtra, "the header's entry size is the kernels'");
-
-int glove_pack_grad_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                        float *packed, int64_t capacity_entries, void *stream)
-{
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    if (!packed) return GLOVE_E_BADARG;
-    if (int rc = plain_table(t, stream)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    IdWork wk = id_work(p);
-    wk.sides = sides_of(h);
-    // header + every distinct id of the selected sides must fit (the plan's capacity bounds the counts not yet known here)
-    const int64_t nr = (wk.sides & 1) ? (p->host_counts[1] >= 0 ? p->host_counts[1] : p->cap_uniq) : 0;
-    const int64_t nc = (wk.sides & 2) ? (p->host_counts[3] >= 0 ? p->host_counts[3] : p->cap_uniq) : 0;
-    if (1 + nr + nc > capacity_entries) return GLOVE_E_WORKSPACE;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    const int nb = apply_blocks(p, shape);
-    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
-    const StepConsts k = make_consts(t, h);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    hipStream_t st = (hipStream_t)stream;
-#define CALL(LPR, NV)                                                                                       \
-    hipLaunchKernelGGL((pack_grad_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, d4, k, packed, \
-                       w.blockpart, nb_row)
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
-#undef CALL
-    return (int)hipGetLastError();
-}
 
 // The passes can write packed-list entries themselves when the plan has chunk records (run-merged schedule) and its
 // counts are known on the host (the col side's entries start behind the row side's).
@@ -2541,52 +2572,56 @@ static bool packing_ok(const glove_plan *p)
     return p->r_crec && p->c_crec && p->host_counts[1] >= 0 && p->host_counts[3] >= 0;
 }
 
+// header + every distinct id of the selected sides must fit (the plan's capacity bounds the counts not yet known here)
+static bool packed_fits(const StepCall &c, int64_t capacity_entries)
+{
+    const glove_plan *p = c.p;
+    const int64_t nr = (c.sides & 1) ? (p->host_counts[1] >= 0 ? p->host_counts[1] : p->cap_uniq) : 0;
+    const int64_t nc = (c.sides & 2) ? (p->host_counts[3] >= 0 ? p->host_counts[3] : p->cap_uniq) : 0;
+    return 1 + nr + nc <= capacity_entries;
+}
+
+// The batch's gradients as a packed list: of every id, or (`rest`, where the plan let glove_passes_packing_f32's passes pack) of
+// the ids those passes left
+static int pack_ids(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes, float *packed,
+                    int64_t capacity_entries, void *stream, bool rest)
+{
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (!packed) return GLOVE_E_BADARG;
+    if (!packed_fits(c, capacity_entries)) return GLOVE_E_WORKSPACE;
+    if (int rc = plain_table(t, stream)) return rc;
+    const bool behind = rest && packing_ok(p);
+    const IdLaunch l = id_launch(c, c.sides, behind && (c.sides & 1) ? kFusePack : kFuseNone, behind && (c.sides & 2) ? kFusePack : kFuseNone);
+#define CALL(LPR, NV)                                                                                                      \
+    hipLaunchKernelGGL((pack_grad_kernel<LPR, NV>), dim3(l.nb), dim3(kBlock), 0, c.st, l.wk, l.rs, l.cs, c.d4, c.k, packed, \
+                       c.w.blockpart, l.nb_row)
+    GLOVE_DISPATCH_ROW_SHAPE(c.shape, CALL);
+#undef CALL
+    return (int)hipGetLastError();
+}
+
+int glove_pack_grad_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
+                        float *packed, int64_t capacity_entries, void *stream)
+{
+    return pack_ids(p, t, h, ws, ws_bytes, packed, capacity_entries, stream, false);
+}
+
 int glove_passes_packing_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                              float *packed, int64_t capacity_entries, void *stream)
 {
-    if (!p || !h) return GLOVE_E_BADARG;
-    if (int rc = plain_table(t, stream)) return rc;
-    const int sides = sides_of(h);
-    if (!packing_ok(p)) return launch_passes(p, t, h, ws, ws_bytes, stream, sides);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (!packing_ok(p)) return passes_on_plain_table(c, PassOpts(c.sides));
     if (!packed) return GLOVE_E_BADARG;
-    const int64_t nr = (sides & 1) ? p->host_counts[1] : 0, nc = (sides & 2) ? p->host_counts[3] : 0;
-    if (1 + nr + nc > capacity_entries) return GLOVE_E_WORKSPACE;
-    return launch_passes(p, t, h, ws, ws_bytes, stream, sides, nullptr, nullptr, false, (sides & 1) ? kFusePack : kFuseNone,
-                         (sides & 2) ? kFusePack : kFuseNone, false, packed);
+    if (!packed_fits(c, capacity_entries)) return GLOVE_E_WORKSPACE;
+    return passes_on_plain_table(c, PassOpts(c.sides).packing(packed));
 }
 
 int glove_pack_rest_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                         float *packed, int64_t capacity_entries, void *stream)
 {
-    if (!p) return GLOVE_E_BADARG;
-    if (!packing_ok(p)) return glove_pack_grad_f32(p, t, h, ws, ws_bytes, packed, capacity_entries, stream);
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    if (!packed) return GLOVE_E_BADARG;
-    if (int rc = plain_table(t, stream)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
-    IdWork wk = id_work(p);
-    wk.sides = sides_of(h);
-    const int64_t nr = (wk.sides & 1) ? p->host_counts[1] : 0, nc = (wk.sides & 2) ? p->host_counts[3] : 0;
-    if (1 + nr + nc > capacity_entries) return GLOVE_E_WORKSPACE;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    const int lpr = pick_pass_shape(d4).lpr;
-    wk.pre_r = (wk.sides & 1) ? kFusePack : kFuseNone;
-    wk.pre_c = (wk.sides & 2) ? kFusePack : kFuseNone;
-    wk.per = fuse_per(p, lpr);
-    const int nb = apply_blocks(p, shape);
-    // the loss partials: of the packing row pass (its grid), or folded by glove_rowside_step_adagrad_f32 (any count reads them)
-    const int nb_row = fusepass_blocks(p, lpr, wk.per, true);
-    const StepConsts k = make_consts(t, h);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    hipStream_t st = (hipStream_t)stream;
-#define CALL(LPR, NV)                                                                                       \
-    hipLaunchKernelGGL((pack_grad_kernel<LPR, NV>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, d4, k, packed, \
-                       w.blockpart, nb_row)
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
-#undef CALL
-    return (int)hipGetLastError();
+    return pack_ids(p, t, h, ws, ws_bytes, packed, capacity_entries, stream, true);
 }
 
 int glove_loss_partials_f32(const glove_plan *p, const glove_tables *t, void *ws, size_t ws_bytes, float *out4, void *stream)
@@ -2618,6 +2653,33 @@ static bool to_list(const glove_packed_list *in, PackedList &out)
     return true;
 }
 
+// Every list is one a kernel can take: asked before the first launch over any of them
+static int check_lists(const glove_packed_list *lists, int32_t n_lists)
+{
+    PackedList pl;
+    for (int32_t i = 0; i < n_lists; ++i)
+        if (!to_list(lists + i, pl)) return GLOVE_E_BADARG;
+    return 0;
+}
+
+// The (checked) lists eight at a time, as a launch sees them: f(index of the batch's first list, the batch, the most entries one of
+// its lists can hold — a list with a header holds up to capacity_entries)
+extern "C++" template <class F>
+static void for_each_list_batch(const glove_packed_list *lists, int32_t n_lists, int64_t capacity_entries, F f)
+{
+    for (int32_t first = 0; first < n_lists; first += 8) {
+        PackedLists pls;
+        pls.n = n_lists - first < 8 ? n_lists - first : 8;
+        int64_t n_max = 0;
+        for (int i = 0; i < pls.n; ++i) {
+            to_list(lists + first + i, pls.l[i]);
+            const int64_t n = pls.l[i].header ? capacity_entries : pls.l[i].n_host;
+            n_max = n > n_max ? n : n_max;
+        }
+        f(first, pls, n_max);
+    }
+}
+
 int glove_combine_packed_f32(const glove_packed_list *list, int32_t tag, const glove_tables *t, float *G_flat,
                              int32_t *mark, int64_t capacity_entries, void *stream)
 {
@@ -2643,20 +2705,13 @@ int glove_count_packed_f32(const glove_packed_list *lists, int32_t n_lists, cons
     DenseViews dv;
     if (int rc = packed_common(t, G_flat, mark, dv)) return rc;
     if (!lists || n_lists < 1 || n_lists > kMarkCountMask || capacity_entries < 0) return GLOVE_E_BADARG;
+    if (int rc = check_lists(lists, n_lists)) return rc;
     const int d4 = t->d / 4;
     hipStream_t st = (hipStream_t)stream;
-    for (int32_t first = 0; first < n_lists; first += 8) {
-        PackedLists pls;
-        pls.n = n_lists - first < 8 ? n_lists - first : 8;
-        int64_t n_max = 0;
-        for (int i = 0; i < pls.n; ++i) {
-            if (!to_list(lists + first + i, pls.l[i])) return GLOVE_E_BADARG;
-            const int64_t n = pls.l[i].header ? capacity_entries : pls.l[i].n_host;
-            n_max = n > n_max ? n : n_max;
-        }
+    for_each_list_batch(lists, n_lists, capacity_entries, [&](int32_t, const PackedLists &pls, int64_t n_max) {
         if (n_max > 0)
             hipLaunchKernelGGL(count_packed_kernel, dim3(blocks_for(n_max, kBlock), pls.n), dim3(kBlock), 0, st, pls, dv, d4);
-    }
+    });
     return (int)hipGetLastError();
 }
 
@@ -2674,6 +2729,7 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
     const bool decays = opt == GLOVE_OPT_NADAM || opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_RMSPROP;
     if (int rc = check_optimizer(t, h, 3, opt)) return rc;
     if (h->sweep_sides < 0 || h->sweep_sides > 3) return GLOVE_E_BADARG;
+    if (int rc = check_lists(lists, n_lists)) return rc;
     const OptHyper oh = opt_consts(h);
     const SlotTwo s2 = slot_two(t);
     if (int rc = plain_table(t, stream)) return rc;
@@ -2690,13 +2746,9 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
     if (!tail && n_lists > 8 && do_scalars) {
         // a launch sees eight lists: sum the loss partials of all headers first (list order, so the sum is repeatable)
         scratch = G_flat + grad_layout(v_row(t), t->V, t->d).tail + 4;
-        for (int32_t first = 0; first < n_lists; first += 8) {
-            PackedLists pls;
-            pls.n = n_lists - first < 8 ? n_lists - first : 8;
-            for (int i = 0; i < pls.n; ++i)
-                if (!to_list(lists + first + i, pls.l[i])) return GLOVE_E_BADARG;
+        for_each_list_batch(lists, n_lists, capacity_entries, [&](int32_t first, const PackedLists &pls, int64_t) {
             hipLaunchKernelGGL(sum_headers_kernel, dim3(1), dim3(64), 0, st, pls, scratch, first == 0 ? 1 : 0);
-        }
+        });
         tail = scratch;
     }
     if (decays) {
@@ -2714,15 +2766,7 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
         if (hi > lo) GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
 #undef CALL
     }
-    for (int32_t first = 0; first < n_lists; first += 8) {
-        PackedLists pls;
-        pls.n = n_lists - first < 8 ? n_lists - first : 8;
-        int64_t n_max = 0;
-        for (int i = 0; i < pls.n; ++i) {
-            if (!to_list(lists + first + i, pls.l[i])) return GLOVE_E_BADARG;
-            const int64_t n = pls.l[i].header ? capacity_entries : pls.l[i].n_host;
-            n_max = n > n_max ? n : n_max;
-        }
+    for_each_list_batch(lists, n_lists, capacity_entries, [&](int32_t first, const PackedLists &pls, int64_t n_max) {
         const int nbx = blocks_for(n_max > 0 ? n_max : 1, kBlock / shape.lpr);
         const int scal = first == 0 ? do_scalars : 0;
 #define CALL(LPR, NV)                                                                                                         \
@@ -2732,9 +2776,10 @@ int glove_apply_packed_adagrad_f32(const glove_packed_list *lists, int32_t n_lis
                                cs, s2, d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, (int)first, tail, t->scalars,    \
                                loss_out, scal);                                                                               \
         })
-        GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+        GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);      // (packed_common has seen the shape: the macro's own refusal cannot come)
 #undef CALL
-    }
+        return 0;
+    });
     if (scratch) {
         hipError_t e = zero_words(scratch, 4, st);      // the tail is all zero between steps
         if (e != hipSuccess) return (int)e;
@@ -2819,24 +2864,25 @@ static int launch_tagged_chain(const glove_plan *const *plans, int n, const glov
 {
     if (!plans || n < 1 || !t || !h || !ws) return GLOVE_E_BADARG;
     const bool adam = opt == GLOVE_OPT_ADAM;
-    const int d4 = t->d / 4;
+    StepCall c;         // one per plan; behind the loop the last one's, of which the launches take what no plan changes
     int most_blocks = 1;
     for (int i = 0; i < n; ++i) {
         const glove_plan *p = plans[i];
-        if (int rc = check_common(p, t, h, ws)) return rc;
+        if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream, false)) return rc;       // (the workspace holds chain records)
         if (adam ? !adam_one_launch(p, t, h) : (!t->R_tag || !t->C_tag || !p->r_crec || !p->c_crec)) return GLOVE_E_BADARG;
-        const int rb = rowpass_blocks(p, pick_pass_shape(d4).lpr);
+        const int rb = rowpass_blocks(p, c.pass.lpr);
         most_blocks = rb > most_blocks ? rb : most_blocks;
     }
-    if (sides_of(h) != 3) return GLOVE_E_BADARG;
+    if (c.sides != 3) return GLOVE_E_BADARG;
     if (int rc = check_optimizer(t, h, 3, opt)) return rc;
     const size_t rec_floats = (size_t)kChainHead + (size_t)kPartials * most_blocks;
     const size_t fit = ws_bytes / (rec_floats * sizeof(float));
     if (fit < 1) return GLOVE_E_WORKSPACE;
-    const RowShape shape = pick_pass_shape(d4);
-    const StepConsts kc = make_consts(t, h);
+    const int d4 = c.d4;
+    const RowShape shape = c.pass;
+    const StepConsts &kc = c.k;
     const OptHyper oh = opt_consts(h);
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = c.st;
     float *recs = (float *)ws;
     // Adam's sweep over all other rows: its part of the grid as adam_fused_kernel's, behind a multiple of 8 workgroups, so that
     // every step's sweep finds the rows it wrote last step in the same L2s
@@ -2884,6 +2930,11 @@ int glove_step_adagrad_f32(const glove_plan *p, const glove_tables *t, const glo
 {
     const int form = pick_step_form(p, t, h);
     if (form == GLOVE_STEP_TAGGED) return launch_tagged_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAGRAD);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    // every form ends in the apply launch, which needs the slots; the twin form needs the version bytes
+    if (form < GLOVE_STEP_TWO_LAUNCH || form > GLOVE_STEP_FUSED_TWIN || !has_slot1(t)) return GLOVE_E_BADARG;
+    if (form == GLOVE_STEP_FUSED_TWIN && !t->R_ver) return GLOVE_E_BADARG;
     // only the twin form follows the version bytes of a twinned row table: every other form first brings it home
     // (a step of another form behind a twin step would otherwise read and write copy 0 of rows whose current copy is the second)
     if (form != GLOVE_STEP_FUSED_TWIN)
@@ -2892,51 +2943,45 @@ int glove_step_adagrad_f32(const glove_plan *p, const glove_tables *t, const glo
     case GLOVE_STEP_FUSED_ONE_PASS:
         // (tests / comparisons) both sides in one launch: neither table may change under the other side's gathers, so both put
         // their finished rows into the slots and the apply launch moves them
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3, nullptr, nullptr, false, kFuseSlot, kFuseSlot)) return rc;
-        return launch_apply_adagrad(p, t, h, ws, ws_bytes, loss_out, stream, kFuseSlot, kFuseSlot);
+        if (int rc = launch_passes(c, PassOpts(3).fuse(kFuseSlot, kFuseSlot))) return rc;
+        return launch_apply_adagrad(c, loss_out, kFuseSlot, kFuseSlot);
     case GLOVE_STEP_FUSED_THREE_LAUNCH:
         // row side first (C is read only); then the col side alone may update C in place while it gathers the
         // still unchanged R; the apply launch moves the row side's finished rows and does the multi-chunk ids
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1, nullptr, nullptr, false, kFuseSlot, kFuseNone)) return rc;
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 2, nullptr, nullptr, false, kFuseNone, kFuseInPlace)) return rc;
-        return launch_apply_adagrad(p, t, h, ws, ws_bytes, loss_out, stream, kFuseSlot, kFuseInPlace);
-    case GLOVE_STEP_FUSED_TWIN:
+        if (int rc = launch_passes(c, PassOpts(1).fuse(kFuseSlot, kFuseNone))) return rc;
+        if (int rc = launch_passes(c, PassOpts(2).fuse(kFuseNone, kFuseInPlace))) return rc;
+        return launch_apply_adagrad(c, loss_out, kFuseSlot, kFuseInPlace);
+    case GLOVE_STEP_FUSED_TWIN: {
         // as the three-launch form, but the row side writes its new rows into the other copy of the twinned row table:
         // the col side keeps gathering the old rows from the current copy, and the apply launch only flips versions
-        if (!t->R_ver) return GLOVE_E_BADARG;
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1, nullptr, nullptr, false, kFuseTwin, kFuseNone, true)) return rc;
-        {
-            // (the list of ids for the apply launch rides in the col-side launch when both sides step and the workspace has the list)
-            const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-            const bool tail = w.work != nullptr && sides_of(h) == 3;
-            if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 2, nullptr, nullptr, false, kFuseNone, kFuseInPlace, true, nullptr, tail)) return rc;
-            return launch_apply_adagrad(p, t, h, ws, ws_bytes, loss_out, stream, kFuseTwin, kFuseInPlace, tail);
-        }
-    case GLOVE_STEP_TWO_LAUNCH:
-        break;
-    default:
-        return GLOVE_E_BADARG;
+        if (int rc = launch_passes(c, PassOpts(1).fuse(kFuseTwin, kFuseNone).on_twin())) return rc;
+        // (the list of ids for the apply launch rides in the col-side launch when both sides step and the workspace has the list)
+        const bool tail = c.w.work != nullptr && c.sides == 3;
+        if (int rc = launch_passes(c, PassOpts(2).fuse(kFuseNone, kFuseInPlace).on_twin(tail))) return rc;
+        return launch_apply_adagrad(c, loss_out, kFuseTwin, kFuseInPlace, tail);
     }
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3)) return rc;
-    return launch_apply_adagrad(p, t, h, ws, ws_bytes, loss_out, stream, kFuseNone, kFuseNone);
+    default:        // GLOVE_STEP_TWO_LAUNCH
+        if (int rc = launch_passes(c, PassOpts(3))) return rc;
+        return launch_apply_adagrad(c, loss_out, kFuseNone, kFuseNone);
+    }
 }
 
 int glove_rowside_step_adagrad_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                                    void *stream)
 {
-    if (!p || !t || !h || sides_of(h) != 1) return GLOVE_E_BADARG;          // hyper.sides = 1: this is the row side's step
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (c.sides != 1 || !has_slot1(t)) return GLOVE_E_BADARG;              // hyper.sides = 1: this is the row side's step
     if (int rc = plain_table(t, stream)) return rc;
     if (!p->r_crec || !p->c_crec) {
         // no chunk records: the row pass stores its partial rows, the apply launch does every row id
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
-        return launch_apply_adagrad(p, t, h, ws, ws_bytes, nullptr, stream, kFuseNone, kFuseNone);
+        if (int rc = launch_passes(c, PassOpts(1))) return rc;
+        return launch_apply_adagrad(c, nullptr, kFuseNone, kFuseNone);
     }
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1, nullptr, nullptr, false, kFuseInPlace, kFuseNone)) return rc;
-    if (int rc = launch_apply_adagrad(p, t, h, ws, ws_bytes, nullptr, stream, kFuseInPlace, kFuseNone)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    const int lpr = pick_pass_shape(t->d / 4).lpr;
-    const int nb_fused = fusepass_blocks(p, lpr, fuse_per(p, lpr), true);
-    hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, w.blockpart, nb_fused);
+    if (int rc = launch_passes(c, PassOpts(1).fuse(kFuseInPlace, kFuseNone))) return rc;
+    if (int rc = launch_apply_adagrad(c, nullptr, kFuseInPlace, kFuseNone)) return rc;
+    const int nb_fused = fusepass_blocks(p, c.pass.lpr, fuse_per(p, c.pass.lpr), true);
+    hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, c.st, c.w.blockpart, nb_fused);
     return (int)hipGetLastError();
 }
 
@@ -2975,63 +3020,65 @@ int glove_canonicalize_f32(const glove_tables *t, void *stream)
     return (int)hipGetLastError();
 }
 
-int glove_steps_adagrad_f32(const glove_plan *const *plans, int32_t n, const glove_tables *t, const glove_hyper *h,
-                            void *ws, size_t ws_bytes, float *loss_out, void *stream)
+// n steps on one set of tables: runs of consecutive steps that take the one-launch form of `opt` (`chained` says so of a plan) go
+// out as chains, one launch per step (launch_tagged_chain); every other step on its own (`single`); the last one writes loss_out
+extern "C++" template <class Chained, class Single>
+static int steps_in_chains(const glove_plan *const *plans, int32_t n, const glove_tables *t, const glove_hyper *h, void *ws,
+                           size_t ws_bytes, float *loss_out, void *stream, int opt, Chained chained, Single single)
 {
     if (!plans || n < 0) return GLOVE_E_BADARG;
-    // runs of consecutive steps that take the tagged form go out as chains: one launch per step
     for (int32_t i = 0; i < n;) {
         int32_t k = i;
-        while (k < n && plans[k] && pick_step_form(plans[k], t, h) == GLOVE_STEP_TAGGED) ++k;
+        while (k < n && chained(plans[k])) ++k;
         if (k > i) {
-            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream, GLOVE_OPT_ADAGRAD)) return rc;
+            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream, opt)) return rc;
             i = k;
             continue;
         }
-        if (int rc = glove_step_adagrad_f32(plans[i], t, h, ws, ws_bytes, i == n - 1 ? loss_out : nullptr, stream)) return rc;
+        if (int rc = single(plans[i], i == n - 1 ? loss_out : nullptr)) return rc;
         ++i;
     }
     return 0;
 }
 
+int glove_steps_adagrad_f32(const glove_plan *const *plans, int32_t n, const glove_tables *t, const glove_hyper *h,
+                            void *ws, size_t ws_bytes, float *loss_out, void *stream)
+{
+    return steps_in_chains(plans, n, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAGRAD,
+                           [&](const glove_plan *p) { return pick_step_form(p, t, h) == GLOVE_STEP_TAGGED; },
+                           [&](const glove_plan *p, float *loss) { return glove_step_adagrad_f32(p, t, h, ws, ws_bytes, loss, stream); });
+}
+
 // passes (marking the batch's ids) + adam_fused_kernel: see the kernel's header.  which = 1: the row side alone (the row pass,
 // the row ids' apply, the sweep over R's rows; no scalar work — glove_rowside_step_f32, whose G_flat IS the V_row marks), 3: both
 // sides (the marks in G_flat's bias segments)
-static int step_adam_fused(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                           float *G_flat, float *loss_out, void *stream, bool nadam = false, int which = 3)
+static int step_adam_fused(const StepCall &c, float *G_flat, float *loss_out, bool nadam = false, int which = 3)
 {
-    if (int rc = check_common(p, t, h, ws)) return rc;
+    const glove_tables *t = c.t;
     if (!G_flat) return GLOVE_E_BADARG;
-    if (int rc = check_optimizer(t, h, 3, nadam ? GLOVE_OPT_NADAM : GLOVE_OPT_ADAM)) return rc;     // (both sides' slots, whichever step)
+    if (int rc = check_optimizer(t, c.h, 3, nadam ? GLOVE_OPT_NADAM : GLOVE_OPT_ADAM)) return rc;     // (both sides' slots, whichever step)
+    if (int rc = plain_table(t, c.st)) return rc;
     const int32_t Vr = v_row(t);
     const GradLayout L = grad_layout(Vr, t->V, t->d);
     float *mark_rows = which & 2 ? G_flat + L.G_br : G_flat, *mark_cols = which & 2 ? G_flat + L.G_bc : nullptr;
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, which, mark_rows, mark_cols)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    IdWork wk = id_work(p);
-    wk.sides = which;
+    if (int rc = launch_passes(c, PassOpts(which).marks(mark_rows, mark_cols))) return rc;
+    const IdLaunch l = id_launch(c, which);
     const int32_t Vc = which & 2 ? t->V : 0;         // col rows the sweep covers (behind R's rows)
     // a multiple of 8 workgroups in front: workgroups b and b + 8 share an XCD, so every step's sweep then finds
     // the rows it wrote last step in the same L2s, whatever the batch's id count (5.3 vs 11 us per launch)
-    const int nb_apply = (apply_blocks(p, shape) + 7) & ~7;
-    const int nb = nb_apply + blocks_for(((int64_t)Vr + Vc + kSweepRows - 1) / kSweepRows, kBlock / shape.lpr);
-    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
-    const StepConsts k = make_consts(t, h);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    const OptHyper oh = opt_consts(h);
-    hipStream_t st = (hipStream_t)stream;
+    const int nb_apply = (l.nb + 7) & ~7;
+    const int nb = nb_apply + blocks_for(((int64_t)Vr + Vc + kSweepRows - 1) / kSweepRows, kBlock / c.shape.lpr);
+    const OptHyper oh = opt_consts(c.h);
 #define CALL(LPR, NV)                                                                                                  \
     dispatch_opt<GLOVE_OPT_ADAM, GLOVE_OPT_NADAM>(nadam ? GLOVE_OPT_NADAM : GLOVE_OPT_ADAM, [&](auto o_) {            \
-        hipLaunchKernelGGL((adam_fused_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, slot_two(t), \
-                           d4, k, oh.b1, oh.b2, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,             \
-                           (const float *)w.blockpart, nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc, nb_apply, loss_out); \
+        hipLaunchKernelGGL((adam_fused_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, c.st, l.wk, l.rs, l.cs, slot_two(t), \
+                           c.d4, c.k, oh.b1, oh.b2, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,         \
+                           (const float *)c.w.blockpart, l.nb_row, mark_rows, mark_cols, (int)Vr, (int)Vc, nb_apply, loss_out); \
     })
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+    GLOVE_DISPATCH_ROW_SHAPE(c.shape, CALL);
 #undef CALL
     if (which == 1)         // the row pass's loss partials, folded: any later reader finds them whatever grid it assumes
-        hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, st, w.blockpart, nb_row);
+        hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, c.st, c.w.blockpart, l.nb_row);
     return (int)hipGetLastError();
 }
 
@@ -3041,43 +3088,33 @@ int glove_step_adam_f32(const glove_plan *p, const glove_tables *t, const glove_
     if (adam_one_launch(p, t, h)) return launch_tagged_chain(&p, 1, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAM);
     // a batch that touches a minority of the rows (the reference's 1,024 pairs): two launches, no gradient buffer
     // traffic; a batch that touches most rows: the dense form, whose sweep then wastes nothing
-    if (int rc = plain_table(t, stream)) return rc;
-    if (p && t && h && sides_of(h) == 3 && 2 * p->B <= (int64_t)v_row(t) + t->V)
-        return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, loss_out, stream);
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3)) return rc;
-    if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
-    return glove_dense_adam_f32(t, h, G_flat, loss_out, stream);
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (c.sides == 3 && 2 * p->B <= (int64_t)v_row(t) + t->V) return step_adam_fused(c, G_flat, loss_out);
+    return dense_step(c, 3, G_flat, loss_out);
 }
 
 // A step of the per-row optimizers (SGD, Adamax, Adadelta, Ftrl, LazyAdam, RowWiseAdagrad): the passes of `sides`, then apply_sparse_opt_kernel on their ids
 // (1: the row ids alone, no scalar work)
-static int launch_sparse_opt_step(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
-                                  int sides, float *loss_out, void *stream)
+static int launch_sparse_opt_step(const StepCall &c, int sides, float *loss_out)
 {
-    const int opt = h->optimizer;
+    const glove_tables *t = c.t;
+    const int opt = c.h->optimizer;
     if (opt != GLOVE_OPT_SGD && opt != GLOVE_OPT_ADAMAX && opt != GLOVE_OPT_ADADELTA && opt != GLOVE_OPT_FTRL && opt != GLOVE_OPT_LAZYADAM &&
         opt != GLOVE_OPT_ROWWISE_ADAGRAD)
         return GLOVE_E_BADARG;
-    if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, sides)) return rc;
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    hipStream_t st = (hipStream_t)stream;
-    const int d4 = t->d / 4;
-    const RowShape shape = pick_row_shape(d4);
-    IdWork wk = id_work(p);
-    wk.sides = sides;
-    const int nb = apply_blocks(p, shape);
-    const int nb_row = rowpass_blocks(p, pick_pass_shape(d4).lpr);
-    const StepConsts k = make_consts(t, h);
-    const SideBufs rs = side_bufs(p, w, t, true), cs = side_bufs(p, w, t, false);
-    const OptHyper oh = opt_consts(h);
+    if (int rc = plain_table(t, c.st)) return rc;
+    if (int rc = launch_passes(c, PassOpts(sides))) return rc;
+    const IdLaunch l = id_launch(c, sides);
+    const OptHyper oh = opt_consts(c.h);
 #define CALL(LPR, NV)                                                                                                      \
     dispatch_opt<GLOVE_OPT_SGD, GLOVE_OPT_ADAMAX, GLOVE_OPT_ADADELTA, GLOVE_OPT_FTRL, GLOVE_OPT_LAZYADAM,                  \
                  GLOVE_OPT_ROWWISE_ADAGRAD>(opt, [&](auto o_) {                                                           \
-        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, decltype(o_)::value>), dim3(nb), dim3(kBlock), 0, st, wk, rs, cs, \
-                           slot_two(t), d4, k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,            \
-                           (const float *)w.blockpart, nb_row, loss_out);                                                 \
+        hipLaunchKernelGGL((apply_sparse_opt_kernel<LPR, NV, decltype(o_)::value>), dim3(l.nb), dim3(kBlock), 0, c.st, l.wk, l.rs, l.cs, \
+                           slot_two(t), c.d4, c.k, oh.o, oh.ln_b1, oh.ln_b2, (const int64_t *)t->step, t->scalars,        \
+                           (const float *)c.w.blockpart, l.nb_row, loss_out);                                             \
     })
-    GLOVE_DISPATCH_ROW_SHAPE(shape, CALL);
+    GLOVE_DISPATCH_ROW_SHAPE(c.shape, CALL);
 #undef CALL
     return (int)hipGetLastError();
 }
@@ -3088,78 +3125,48 @@ int glove_step_sparse_f32(const glove_plan *p, const glove_tables *t, const glov
     if (!h) return GLOVE_E_BADARG;
     if (h->optimizer == GLOVE_OPT_ADAGRAD) return glove_step_adagrad_f32(p, t, h, ws, ws_bytes, loss_out, stream);
     if (h->optimizer == GLOVE_OPT_ADAM) return glove_step_adam_f32(p, t, h, ws, ws_bytes, G_flat, loss_out, stream);
-    if (int rc = plain_table(t, stream)) return rc;
-    if (int rc = check_common(p, t, h, ws)) return rc;
-    if (sides_of(h) != 3) return GLOVE_E_BADARG;
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (c.sides != 3) return GLOVE_E_BADARG;
     if (int rc = check_optimizer(t, h, 3, h->optimizer)) return rc;
     if (h->optimizer == GLOVE_OPT_NADAM)        // passes (marking the batch's ids) + one kernel: apply for the ids, decay of m and v for all other rows
-        return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, loss_out, stream, true);
-    hipStream_t st = (hipStream_t)stream;
-    const StepConsts k = make_consts(t, h);
-    if (h->optimizer == GLOVE_OPT_RMSPROP) {
-        if (!G_flat) return GLOVE_E_BADARG;
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 3)) return rc;
-        if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
-        DenseSegs segs; float *tail; int nbx, sides;
-        if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
-        hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, h->rho, t->scalars, tail, loss_out, 1);
-        return (int)hipGetLastError();
-    }
-    return launch_sparse_opt_step(p, t, h, ws, ws_bytes, 3, loss_out, stream);
+        return step_adam_fused(c, G_flat, loss_out, true);
+    if (h->optimizer == GLOVE_OPT_RMSPROP) return dense_step(c, 3, G_flat, loss_out);
+    return launch_sparse_opt_step(c, 3, loss_out);
 }
 
 int glove_rowside_step_f32(const glove_plan *p, const glove_tables *t, const glove_hyper *h, void *ws, size_t ws_bytes,
                            float *G_flat, void *stream)
 {
-    if (!p || !t || !h || sides_of(h) != 1) return GLOVE_E_BADARG;          // hyper.sides = 1: this is the row side's step
+    if (!h) return GLOVE_E_BADARG;
     if (h->optimizer == GLOVE_OPT_ADAGRAD) return glove_rowside_step_adagrad_f32(p, t, h, ws, ws_bytes, stream);
-    if (int rc = plain_table(t, stream)) return rc;
-    if (int rc = check_common(p, t, h, ws)) return rc;
+    StepCall c;
+    if (int rc = open_call(c, p, t, h, ws, ws_bytes, stream)) return rc;
+    if (c.sides != 1) return GLOVE_E_BADARG;                                 // hyper.sides = 1: this is the row side's step
     if (!t->s1_R || !t->s1_br) return GLOVE_E_BADARG;
     const int opt = h->optimizer;
     if (opt == GLOVE_OPT_ADAM || opt == GLOVE_OPT_NADAM)
         // the row pass marks the batch's row ids; one kernel applies them and gives every other row of the shard its G = 0 update
-        return step_adam_fused(p, t, h, ws, ws_bytes, G_flat, nullptr, stream, opt == GLOVE_OPT_NADAM, 1);
-    const StepWs w = carve_step_ws(ws, p->B, p->cap_chunks, t->d);
-    if (w.bytes > ws_bytes) return GLOVE_E_WORKSPACE;
+        return step_adam_fused(c, G_flat, nullptr, opt == GLOVE_OPT_NADAM, 1);
     if (int rc = check_optimizer(t, h, 1, opt)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const StepConsts k = make_consts(t, h);
-    const int nb_row = rowpass_blocks(p, pick_pass_shape(t->d / 4).lpr);
     if (opt == GLOVE_OPT_RMSPROP) {
         // the row half of glove_step_sparse_f32's RMSprop: the summed row gradients into G_flat, the sweep over R's rms slot
-        if (!G_flat) return GLOVE_E_BADARG;
-        if (int rc = launch_passes(p, t, h, ws, ws_bytes, stream, 1)) return rc;
-        if (int rc = launch_dense_grad(p, t, h, ws, ws_bytes, G_flat, stream)) return rc;
-        DenseSegs segs; float *tail; int nbx, sides;
-        if (int rc = dense_common(t, h, G_flat, false, segs, tail, nbx, sides)) return rc;
-        hipLaunchKernelGGL(dense_rmsprop_kernel, dim3(nbx, 4), dim3(kBlock), 0, st, segs, k, h->rho, t->scalars, tail, nullptr, 0);
+        if (int rc = dense_step(c, 1, G_flat, nullptr)) return rc;
     } else {
         // the per-row optimizers: the row pass, then their epilogue on the row ids (apply_sparse_opt_kernel, sides 1: no scalar work)
-        if (int rc = launch_sparse_opt_step(p, t, h, ws, ws_bytes, 1, nullptr, stream)) return rc;
+        if (int rc = launch_sparse_opt_step(c, 1, nullptr)) return rc;
     }
     // the row pass's loss partials, folded: glove_loss_partials_f32 / the col side's dense gradient find them whatever grid they assume
-    hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, st, w.blockpart, nb_row);
+    hipLaunchKernelGGL(fold_blockpart_kernel, dim3(1), dim3(kBlock), 0, c.st, c.w.blockpart, rowpass_blocks(p, c.pass.lpr));
     return (int)hipGetLastError();
 }
 
 int glove_steps_adam_f32(const glove_plan *const *plans, int32_t n, const glove_tables *t, const glove_hyper *h,
                          void *ws, size_t ws_bytes, float *G_flat, float *loss_out, void *stream)
 {
-    if (!plans || n < 0) return GLOVE_E_BADARG;
-    // runs of consecutive steps that take the one-launch form go out as chains
-    for (int32_t i = 0; i < n;) {
-        int32_t k = i;
-        while (k < n && adam_one_launch(plans[k], t, h)) ++k;
-        if (k > i) {
-            if (int rc = launch_tagged_chain(plans + i, k - i, t, h, ws, ws_bytes, k == n ? loss_out : nullptr, stream, GLOVE_OPT_ADAM)) return rc;
-            i = k;
-            continue;
-        }
-        if (int rc = glove_step_adam_f32(plans[i], t, h, ws, ws_bytes, G_flat, i == n - 1 ? loss_out : nullptr, stream)) return rc;
-        ++i;
-    }
-    return 0;
+    return steps_in_chains(plans, n, t, h, ws, ws_bytes, loss_out, stream, GLOVE_OPT_ADAM,
+                           [&](const glove_plan *p) { return adam_one_launch(p, t, h); },
+                           [&](const glove_plan *p, float *loss) { return glove_step_adam_f32(p, t, h, ws, ws_bytes, G_flat, loss, stream); });
 }
 
 

@@ -745,19 +745,29 @@ static void dispatch_bool(bool on, F f)
 }
 
 
-// What launch_passes (glove_step.hip) has worked out, as the objects that hold sidepass_kernel's builds take it
-struct PassLaunch {
+// One call on the step path: its arguments, validated once by the entry point that opens it (open_call, glove_step.hip), and
+// what every launcher behind it would otherwise derive from them again
+struct StepCall {
     const glove_plan *p;
     const glove_tables *t;
     const glove_hyper *h;
-    PassSide rs, cs;
-    StepWs w;
-    StepConsts kc;
-    ListTail tail;
-    RowShape shape;
-    int d4, per, row_blocks, nb, nb_launch, which;
-    bool twin, solid, streaming, rec, pack, fuse;
+    void *ws;
+    size_t ws_bytes;
     hipStream_t st;
+    StepWs w;                   // the workspace, carved
+    int d4;
+    RowShape shape, pass;       // pick_row_shape / pick_pass_shape of d4
+    int sides;                  // glove_hyper.sides: 1 rows, 2 cols, 3 both
+    StepConsts k;
+};
+
+// What launch_passes (glove_step.hip) has worked out, as the objects that hold sidepass_kernel's builds take it
+struct PassLaunch {
+    const StepCall &c;
+    PassSide rs, cs;
+    ListTail tail;
+    int per, row_blocks, nb, nb_launch, which;
+    bool twin, solid, streaming, rec, pack, fuse;
 };
 
 // The launch of sidepass_kernel's builds for the shapes <LA, NA> and <LB, NB>: the object that calls it holds them, and no other may
@@ -765,16 +775,16 @@ template <int LA, int NA, int LB, int NB>
 static int launch_pass_shapes(const PassLaunch &a)
 {
     static_assert(pass_shape_listed(RowShape{LA, NA}) && pass_shape_listed(RowShape{LB, NB}), "only shapes pick_pass_shape selects are built");
-    const glove_plan *p = a.p;
-    const glove_tables *t = a.t;
-    const glove_hyper *h = a.h;
+    const glove_plan *p = a.c.p;
+    const glove_tables *t = a.c.t;
+    const glove_hyper *h = a.c.h;
     const PassSide &rs = a.rs, &cs = a.cs;
-    const StepWs &w = a.w;
-    const StepConsts &kc = a.kc;
+    const StepWs &w = a.c.w;
+    const StepConsts &kc = a.c.k;
     const ListTail &tail = a.tail;
-    const int d4 = a.d4, per = a.per, row_blocks = a.row_blocks, nb = a.nb, nb_launch = a.nb_launch, which = a.which;
+    const int d4 = a.c.d4, per = a.per, row_blocks = a.row_blocks, nb = a.nb, nb_launch = a.nb_launch, which = a.which;
     const bool twin = a.twin, solid = a.solid, streaming = a.streaming, rec = a.rec, pack = a.pack, fuse = a.fuse;
-    hipStream_t st = a.st;
+    hipStream_t st = a.c.st;
 #define ARGS p->counts, rs, cs, row_blocks, t->scalars, t->step, d4, h->inv_batch, w.blockpart, (int)h->head, h->neg_factor, kc, per, w.work, tail
 // (K: one launch of the build <..., HEAD, SIDE>, in its solid form where the batch calls for it — FUSE == 1 only)
 #define K(LPR, NV, FULL, REC, FUSE, HEAD, SIDE, GRID)                                                                          \
@@ -811,8 +821,8 @@ static int launch_pass_shapes(const PassLaunch &a)
         if (rec) { if (pack) LAUNCH(LPR, NV, FULL, true, 2); else if (fuse) LAUNCH(LPR, NV, FULL, true, 1); else LAUNCH(LPR, NV, FULL, true, 0); } \
         else { if (fuse) LAUNCH(LPR, NV, FULL, false, 1); else LAUNCH(LPR, NV, FULL, false, 0); }        \
     })
-    if (a.shape.lpr == LA && a.shape.nv == NA) CALL(LA, NA);
-    else if (a.shape.lpr == LB && a.shape.nv == NB) CALL(LB, NB);
+    if (a.c.pass.lpr == LA && a.c.pass.nv == NA) CALL(LA, NA);
+    else if (a.c.pass.lpr == LB && a.c.pass.nv == NB) CALL(LB, NB);
     else return GLOVE_E_BADARG;
 #undef CALL
 #undef LAUNCH
