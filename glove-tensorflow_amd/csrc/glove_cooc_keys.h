@@ -38,6 +38,22 @@ __device__ inline void emit_slot_keys(const int32_t *__restrict__ tok, int64_t n
     }
 }
 
+// The run-length encoded keys of a sorted slot array without the sentinel run, counts widened to int64, cut at cap: what a
+// chunk's table (glove_cooc_stream.hip) and a block's bigram table (glove_phrases.hip) are copied out by.  The grid's stride loop.
+__device__ inline void copy_out_runs(const uint64_t *__restrict__ ukeys, const uint32_t *__restrict__ ucounts,
+                                     const int64_t *__restrict__ n_unique, uint64_t *__restrict__ keys_out,
+                                     int64_t *__restrict__ counts_out, int64_t *__restrict__ n_out, int64_t cap)
+{
+    int64_t m = *n_unique;
+    if (m > 0 && ukeys[m - 1] == kNoKey) --m;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = m;
+    if (m > cap) m = cap;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        keys_out[i] = ukeys[i];
+        counts_out[i] = (int64_t)ucounts[i];
+    }
+}
+
 // Workspace of the sort and the run-length encoding of n positions' slots (52 B per slot and the scratch of rocPRIM).
 // head and head_scan belong to the one-shot call's aggregation; a chunk leaves them unused, so both calls ask for the same bytes.
 struct CoocSortWs {

@@ -30,14 +30,7 @@ __global__ void chunk_copy_out(const uint64_t *__restrict__ ukeys, const uint32_
                                const int64_t *__restrict__ n_unique, uint64_t *__restrict__ keys_out,
                                int64_t *__restrict__ counts_out, int64_t *__restrict__ n_out, int64_t cap)
 {
-    int64_t m = *n_unique;
-    if (m > 0 && ukeys[m - 1] == kNoKey) --m;
-    if (blockIdx.x == 0 && threadIdx.x == 0) *n_out = m;
-    if (m > cap) m = cap;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-        keys_out[i] = ukeys[i];
-        counts_out[i] = (int64_t)ucounts[i];
-    }
+    copy_out_runs(ukeys, ucounts, n_unique, keys_out, counts_out, n_out, cap);
 }
 
 }  // namespace glove

@@ -3,7 +3,8 @@
 //     finalisation.  Their kernels are compiled once, in glove_table_ops.hip; the entry points of glove_cooc_stream.hip,
 //     glove_text.hip and glove_cooc_options.hip pack their arguments and call the host drivers declared here (host calls
 //     across objects: no relocatable device code);
-//   - the workspace of a count pass / scan / write pass over tiles, and rocPRIM's scan of the tile counts.
+//   - the workspace of a count pass / scan / write pass over tiles, and rocPRIM's scan of the tile counts (the token filter's, the
+//     phrase selection's; the phrase join carves the same pieces for its running maximum over tiles).
 #pragma once
 #include "glove_merge_path.h"
 

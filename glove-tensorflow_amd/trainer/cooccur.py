@@ -213,7 +213,10 @@ class CoocAccumulator:
         if isinstance(tokens_with_halo, np.ndarray) and hasattr(self.backend, "device"):
             import torch
             tokens_with_halo = torch.from_numpy(np.ascontiguousarray(tokens_with_halo, np.int32)).to(self.backend.device)
-        keys, counts = self.backend.cooc_chunk_keys(tokens_with_halo, int(n_own), self.V, self.context)
+        self.merge_in(*self.backend.cooc_chunk_keys(tokens_with_halo, int(n_own), self.V, self.context))
+
+    def merge_in(self, keys, counts):
+        """Folds one ascending (keys, counts) table into the state (trainer.phrases brings a block's bigram table)."""
         self.chunks += 1
         m = len(keys)
         if self.keys is None:                   # the first chunk is the state (copied: `keys` may be the head of a big buffer)
@@ -322,7 +325,12 @@ def kept_table(lookup: dict, backend=None):
     """The table pass two searches, from the token -> id dict the Python path looks tokens up in: (hashes ascending, as
     the int64 bit patterns of the uint64 values; ids int32; offsets int64 [n + 1]; the words' bytes, concatenated).  Two
     kept words with one hash are a collision the device could not tell apart: ValueError."""
-    words = [(token_hash(tok.encode()), tok.encode(), i) for tok, i in lookup.items()]
+    return kept_table_of_bytes([(tok.encode(), i) for tok, i in lookup.items()], backend)
+
+
+def kept_table_of_bytes(words, backend=None):
+    """`kept_table` from (the word's bytes, its id) pairs: what trainer.phrases keeps, whose words need not decode."""
+    words = [(token_hash(word), word, i) for word, i in words]
     words.sort(key=lambda w: w[0])
     keys = np.asarray([w[0] for w in words], np.uint64)
     if len(keys) > 1 and (keys[1:] == keys[:-1]).any():

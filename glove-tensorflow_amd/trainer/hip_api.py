@@ -45,6 +45,9 @@ VECTORS_MAX_D = 65536               # GLOVE_VECTORS_MAX_D: the most numbers per 
 GLOVE_COOC_OPTIONS_ABI_VERSION = 1  # include/glove_cooc_options_hip.h: the same library's fourth header (token filter, window weightings), versioned on its own
 FILTER_TILE = 4096                  # GLOVE_FILTER_TILE: tokens of a block one workgroup of glove_token_filter_i32 owns
 WINDOW_WEIGHTINGS = {"harmonic": 0, "uniform": 1, "dynamic": 2}      # GLOVE_WINDOW_*
+GLOVE_PHRASES_ABI_VERSION = 1       # include/glove_phrases_hip.h: the same library's fifth header (phrase detection), versioned on its own
+PHRASE_TILE = 1024                  # GLOVE_PHRASE_TILE: tokens of a block one workgroup of glove_phrase_join_u8 owns
+PHRASE_SELECT_TILE = 1024           # GLOVE_PHRASE_SELECT_TILE: keys of a table one workgroup of glove_phrase_select owns
 GLOVE_FACTOR_ABI_VERSION = 1        # include/glove_factor_hip.h (libglove_factor_hip.so)
 FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one lane group of glove_csr_spmm_f32 sums
 GLOVE_FACTOR_DENSE_ABI_VERSION = 1  # include/glove_factor_dense_hip.h: the same library's second header (dense tables), versioned on its own
@@ -114,6 +117,10 @@ VECTORS_EXPORTED_SYMBOLS = ("glove_vectors_abi_version", "glove_vectors_lines_wo
 # every symbol include/glove_cooc_options_hip.h declares (the same library)
 COOC_OPTIONS_EXPORTED_SYMBOLS = ("glove_cooc_options_abi_version", "glove_token_filter_workspace_bytes", "glove_token_filter_i32",
                                  "glove_cooc_finalize_weighted_workspace_bytes", "glove_cooc_finalize_weighted")
+# every symbol include/glove_phrases_hip.h declares (the same library)
+PHRASES_EXPORTED_SYMBOLS = ("glove_phrases_abi_version", "glove_phrase_bigram_workspace_bytes", "glove_phrase_bigram_keys_i32",
+                            "glove_phrase_select_workspace_bytes", "glove_phrase_select", "glove_phrase_join_workspace_bytes",
+                            "glove_phrase_join_u8")
 # every symbol include/glove_factor_hip.h declares (libglove_factor_hip.so)
 FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace_bytes", "glove_csr_spmm_f32",
                            "glove_csr_row_sums_f64", "glove_coo_reweight_f32")
@@ -286,7 +293,7 @@ _prep_lib = None
 
 
 def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h, include/glove_vectors_hip.h, include/glove_cooc_options_hip.h) and declare the prototypes, at the first call that needs
+    """dlopen libglove_prep_hip.so (include/glove_cooc_stream_hip.h, include/glove_text_hip.h, include/glove_vectors_hip.h, include/glove_cooc_options_hip.h, include/glove_phrases_hip.h) and declare the prototypes, at the first call that needs
     it: training never loads it.  Raises if it is not built, like load_library."""
     global _prep_lib
     if _prep_lib is not None and path is None:
@@ -319,6 +326,13 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_token_filter_i32": (C.c_int, [vp, i64, i64, vp, i32, C.c_uint64, vp, vp, i64, vp, sz, vp]),
         "glove_cooc_finalize_weighted_workspace_bytes": (sz, [i64]),
         "glove_cooc_finalize_weighted": (C.c_int, [vp, vp, vp, i64, i32, i32, i64, i32, vp, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_phrases_abi_version": (C.c_int, []),
+        "glove_phrase_bigram_workspace_bytes": (sz, [i64]),
+        "glove_phrase_bigram_keys_i32": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_phrase_select_workspace_bytes": (sz, [i64]),
+        "glove_phrase_select": (C.c_int, [vp, vp, vp, i64, vp, i32, i64, i64, C.c_double, vp, vp, vp, vp, i64, vp, sz, vp]),
+        "glove_phrase_join_workspace_bytes": (sz, [i64]),
+        "glove_phrase_join_u8": (C.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp, i64, i32, vp, vp, vp, vp, sz, vp]),
     }
     lib = _open(Path(path) if path else PREP_LIB_PATH, protos)
     if lib.glove_cooc_stream_abi_version() != GLOVE_COOC_STREAM_ABI_VERSION:
@@ -333,6 +347,9 @@ def load_prep_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_cooc_options_abi_version() != GLOVE_COOC_OPTIONS_ABI_VERSION:
         raise GloveHipError("ABI mismatch: prep library (counting-option entry points) %d, binding %d"
                             % (lib.glove_cooc_options_abi_version(), GLOVE_COOC_OPTIONS_ABI_VERSION))
+    if lib.glove_phrases_abi_version() != GLOVE_PHRASES_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: prep library (phrase entry points) %d, binding %d"
+                            % (lib.glove_phrases_abi_version(), GLOVE_PHRASES_ABI_VERSION))
     if path is None:
         _prep_lib = lib
     return lib
@@ -1880,6 +1897,99 @@ class GloveHip:
         sizes = torch.tensor([int(hashes.numel()), 0, 0], dtype=torch.int64).to(hashes.device)
         self.text_token_ids_enqueue(block, start, length, hashes, sizes[0:1], kept, ids, sizes[1:3])
         return ids, int(sizes[1].item())
+
+    # ---- phrase detection (include/glove_phrases_hip.h): what trainer.phrases drives.  Bigram keys travel as int64 tensors
+    # whose bits are the header's uint64 (an id is below 2^31, so they are the same numbers).
+    def phrase_bigram_keys_enqueue(self, block, start, length, ids, n_tokens, keys_out, counts_out, n_out, ws=None):
+        """glove_phrase_bigram_keys_i32 on the current stream, nothing read back: block uint8 [n_bytes]; start / length / ids
+        int32 [cap_tokens]; n_tokens int64 [>= 1]; keys_out / counts_out int64 [cap]; n_out int64 [>= 2]."""
+        lib = load_prep_library()
+        cap_tokens = int(start.numel())
+        _require(block, torch.uint8); _require(start, torch.int32); _require(length, torch.int32, cap_tokens)
+        _require(ids, torch.int32, cap_tokens); _require(n_tokens, torch.int64); _require(keys_out, torch.int64)
+        _require(counts_out, torch.int64, int(keys_out.numel())); _require(n_out, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_phrase_bigram_workspace_bytes(cap_tokens), "glove_phrase_bigram_workspace_bytes")
+        _check(lib.glove_phrase_bigram_keys_i32(_ptr(block) if block.numel() else None, int(block.numel()), _ptr(start),
+                                                _ptr(length), _ptr(ids), _ptr(n_tokens), cap_tokens, _ptr(keys_out),
+                                                _ptr(counts_out), _ptr(n_out), int(keys_out.numel()), _ptr(ws), ws.numel(),
+                                                _stream()), "glove_phrase_bigram_keys_i32")
+
+    def phrase_select_enqueue(self, keys, counts, n, unigram, total_tokens: int, min_count: int, threshold: float, keys_out,
+                              counts_out, score_out, n_out, ws=None):
+        """glove_phrase_select on the current stream, nothing read back: keys / counts int64 [cap_keys], n int64 [>= 1],
+        unigram int64 [V]; keys_out / counts_out int64 [cap_out], score_out float64 [cap_out], n_out int64 [>= 2]."""
+        lib = load_prep_library()
+        cap_keys, cap_out = int(keys.numel()), int(keys_out.numel())
+        _require(keys, torch.int64); _require(counts, torch.int64, cap_keys); _require(n, torch.int64)
+        _require(unigram, torch.int64); _require(keys_out, torch.int64); _require(counts_out, torch.int64, cap_out)
+        _require(score_out, torch.float64, cap_out); _require(n_out, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_phrase_select_workspace_bytes(cap_keys), "glove_phrase_select_workspace_bytes")
+        _check(lib.glove_phrase_select(_ptr(keys), _ptr(counts), _ptr(n), cap_keys, _ptr(unigram), int(unigram.numel()),
+                                       int(total_tokens), int(min_count), float(threshold), _ptr(keys_out), _ptr(counts_out),
+                                       _ptr(score_out), _ptr(n_out), cap_out, _ptr(ws), ws.numel(), _stream()),
+               "glove_phrase_select")
+
+    def phrase_join_enqueue(self, block, start, length, ids, n_tokens, phrase_keys, n_phrases, delimiter: int, carry, joined,
+                            n_joined, ws=None):
+        """glove_phrase_join_u8 on the current stream, nothing read back: block uint8 [n_bytes], rewritten in place; start /
+        length / ids int32 [cap_tokens]; n_tokens, n_phrases int64 [>= 1]; phrase_keys, joined int64 [cap_phrases]; carry
+        int32 [1]; n_joined int64 [>= 2]."""
+        lib = load_prep_library()
+        cap_tokens, cap_phrases = int(start.numel()), int(phrase_keys.numel())
+        _require(block, torch.uint8); _require(start, torch.int32); _require(length, torch.int32, cap_tokens)
+        _require(ids, torch.int32, cap_tokens); _require(n_tokens, torch.int64); _require(phrase_keys, torch.int64)
+        _require(n_phrases, torch.int64); _require(carry, torch.int32, 1); _require(joined, torch.int64, cap_phrases)
+        _require(n_joined, torch.int64)
+        if ws is None:
+            ws = self._bytes(lib.glove_phrase_join_workspace_bytes(cap_tokens), "glove_phrase_join_workspace_bytes")
+        _check(lib.glove_phrase_join_u8(_ptr(block) if block.numel() else None, int(block.numel()), _ptr(start), _ptr(length),
+                                        _ptr(ids), _ptr(n_tokens), cap_tokens, _ptr(phrase_keys) if cap_phrases else None,
+                                        _ptr(n_phrases), cap_phrases, int(delimiter), _ptr(carry),
+                                        _ptr(joined) if cap_phrases else None, _ptr(n_joined), _ptr(ws), ws.numel(), _stream()),
+               "glove_phrase_join_u8")
+
+    def phrase_bigram_keys(self, block, start, length, ids, cap: int | None = None):
+        """(keys int64, counts int64): the distinct bigram keys (id << 32 | next id) of a block's plain adjacent pairs of
+        kept words, ascending, and how often each occurs (one host sync for the size)."""
+        n = int(start.numel())
+        cap = int(cap if cap is not None else max(1, n))
+        keys = torch.empty(cap, dtype=torch.int64, device=block.device)
+        counts = torch.empty_like(keys)
+        sizes = torch.tensor([n, 0, 0], dtype=torch.int64).to(block.device)
+        self.phrase_bigram_keys_enqueue(block, start, length, ids, sizes[0:1], keys, counts, sizes[1:3])
+        m = int(sizes[1].item())
+        if m > cap:
+            raise GloveHipError("the block has %d distinct bigrams, capacity %d" % (m, cap))
+        return keys[:m], counts[:m]
+
+    def phrase_select(self, keys, counts, unigram, total_tokens: int, min_count: int, threshold: float, cap: int | None = None):
+        """(keys int64, counts int64, scores float64): the bigrams with count >= min_count and
+        (count - min_count) / unigram[a] / unigram[b] * total_tokens > threshold, keys ascending (one host sync)."""
+        n = int(keys.numel())
+        cap = int(cap if cap is not None else max(1, n))
+        out_keys = torch.empty(cap, dtype=torch.int64, device=keys.device)
+        out_counts = torch.empty_like(out_keys)
+        scores = torch.empty(cap, dtype=torch.float64, device=keys.device)
+        sizes = torch.tensor([n, 0, 0], dtype=torch.int64).to(keys.device)
+        if n == 0:                       # (a zero-element tensor has no address to hand over)
+            keys = counts = torch.zeros(1, dtype=torch.int64, device=out_keys.device)
+        self.phrase_select_enqueue(keys, counts, sizes[0:1], unigram, total_tokens, min_count, threshold, out_keys, out_counts,
+                                   scores, sizes[1:3])
+        m = int(sizes[1].item())
+        if m > cap:
+            raise GloveHipError("%d phrases are accepted, capacity %d" % (m, cap))
+        return out_keys[:m], out_counts[:m], scores[:m]
+
+    def phrase_join(self, block, start, length, ids, phrase_keys, delimiter: int, carry, joined) -> int:
+        """Rewrites `block` in place: the single space of every chosen pair becomes `delimiter`; carry (int32 [1]) takes the
+        greedy rule from block to block, joined[j] grows by the joins of phrase_keys[j].  -> the block's joins (one host
+        sync)."""
+        sizes = torch.tensor([int(start.numel()), int(phrase_keys.numel()), 0, 0], dtype=torch.int64).to(block.device)
+        self.phrase_join_enqueue(block, start, length, ids, sizes[0:1], phrase_keys, sizes[1:2], delimiter, carry, joined,
+                                 sizes[2:4])
+        return int(sizes[2].item())
 
     # ---- reading and writing word-vector text files (include/glove_vectors_hip.h): what trainer.vectors drives
     def vectors_lines_enqueue(self, block, line_start, line_fields, n_lines, ws=None):
