@@ -11,7 +11,8 @@ Tolerances.  Cosines and centroids: rtol 1e-5, atol 1e-6, the project's figures 
 float64 margin (best minus second-best score) is below 2.5e-5 — twice the tolerance at |cos| <= 1, rounded up — is
 undecided: there the GPU may pick any centroid within 2.5e-5 of the best; everywhere else the assignment is exact.  The
 float64 reference alone leaves at most 0.06 % of a case's points undecided at that threshold with the seeds below (the
-(5000, 64, 5000, 129) case; 0.055 % at (20000, 64, 20000, 4096), none in the others); the cap, asserted first, is 0.5 %."""
+(5000, 64, 5000, 129) case; 0.055 % at (20000, 64, 20000, 4096), none in the others); the cap, asserted first, is 0.5 %.
+The widths here reach three of the seven row shapes; tests/test_gpu_factor_row_shapes.py runs assign and update at all of them."""
 import functools
 import json
 import subprocess

@@ -15,7 +15,8 @@ Tolerances are derived, not measured; u = 2^-24, g(k) = (k + 2) u / (1 - (k + 2)
   - column sums: |got - ref| <= n 2^-53 sum |x| against the exactly rounded float64 sum (math.fsum);
   - transform: a chain of d terms and one subtraction, |got - ref| <= g(d) (sum_k |x_k T_jk| + |shift_j|) + 1e-30;
   - driver: the deviation e_ref of the NumPy float32 backend from the NumPy float64 backend on the same input is the
-    rounding level of the reference itself; the device is allowed 8 e_ref from the float64 result.  Both are printed."""
+    rounding level of the reference itself; the device is allowed 8 e_ref from the float64 result.  Both are printed.
+The widths here stop at five 64-column blocks; tests/test_gpu_factor_row_shapes.py goes on to the limit of sixteen, bit for bit."""
 import functools
 import json
 import math

@@ -12,7 +12,8 @@ Tolerances are derived, not measured:
     rounding level of the reference itself; the device, which sums in another order, with fma and in chunks, is
     allowed 8 e_ref from the float64 result.  Both figures are printed.
 
-At l = 64 a workgroup holds 16 rows, which divides the 20000 rows of the Zipf case: the case `zipf_odd` has 20003."""
+At l = 64 a workgroup holds 16 rows, which divides the 20000 rows of the Zipf case: the case `zipf_odd` has 20003.
+The widths here reach three of the seven row shapes; tests/test_gpu_factor_row_shapes.py runs the product at all of them."""
 import functools
 import json
 import math
