@@ -1,7 +1,7 @@
 """ctypes binding of libglove_hip.so (C ABI: include/glove_hip.h), of libglove_eval_hip.so (include/glove_eval_hip.h,
 include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h), of libglove_prep_hip.so (include/glove_cooc_stream_hip.h,
 include/glove_text_hip.h, include/glove_vectors_hip.h, include/glove_cooc_options_hip.h) and of libglove_factor_hip.so
-(include/glove_factor_hip.h, include/glove_factor_dense_hip.h).
+(include/glove_factor_hip.h, include/glove_factor_dense_hip.h, include/glove_factor_graph_hip.h).
 
 This is the only way the host loop reaches the GPU kernels.  There is no CPU fallback: if the
 shared library is missing or a call fails, an exception is raised.  torch is used here only
@@ -53,6 +53,7 @@ FACTOR_CHUNK = 512                  # GLOVE_FACTOR_CHUNK: nonzeros of a row one 
 GLOVE_FACTOR_DENSE_ABI_VERSION = 1  # include/glove_factor_dense_hip.h: the same library's second header (dense tables), versioned on its own
 GRAM_CHUNK = 1024                   # GLOVE_GRAM_CHUNK: rows of one float32 fmaf chain of glove_gram_f64
 GRAM_SLICE = 16384                  # GLOVE_GRAM_SLICE: rows whose chunk partials one float64 slice partial adds
+GLOVE_FACTOR_GRAPH_ABI_VERSION = 1  # include/glove_factor_graph_hip.h: the same library's third header (retrofitting), versioned on its own
 REWEIGHT_KINDS = {"none": 0, "sqrt": 1, "log1p": 2, "ppmi": 3}      # GLOVE_REWEIGHT_*
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
@@ -127,6 +128,8 @@ FACTOR_EXPORTED_SYMBOLS = ("glove_factor_abi_version", "glove_csr_spmm_workspace
 # every symbol include/glove_factor_dense_hip.h declares (the same library)
 FACTOR_DENSE_EXPORTED_SYMBOLS = ("glove_factor_dense_abi_version", "glove_gram_workspace_bytes", "glove_col_sums_f64",
                                  "glove_gram_f64", "glove_rows_transform_f32")
+# every symbol include/glove_factor_graph_hip.h declares (the same library)
+FACTOR_GRAPH_EXPORTED_SYMBOLS = ("glove_factor_graph_abi_version", "glove_retrofit_rows_f32")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -382,19 +385,33 @@ def factor_dense_prototypes() -> dict:
     }
 
 
+def factor_graph_prototypes() -> dict:
+    """name -> (result, arguments) of every function include/glove_factor_graph_hip.h declares."""
+    i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
+    return {
+        "glove_factor_graph_abi_version": (C.c_int, []),
+        "glove_retrofit_rows_f32": (C.c_int, [vp, vp, vp, i32, i64, vp, i32, vp, vp, vp, i32, C.c_float, vp]),
+    }
+
+
 def load_factor_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_factor_hip.so (include/glove_factor_hip.h, include/glove_factor_dense_hip.h) and declare the
+    """dlopen libglove_factor_hip.so (include/glove_factor_hip.h, include/glove_factor_dense_hip.h,
+    include/glove_factor_graph_hip.h) and declare the
     prototypes, at the first call that needs it: training never loads it.  Raises if it is not built, like load_library."""
     global _factor_lib
     if _factor_lib is not None and path is None:
         return _factor_lib
-    lib = _open(Path(path) if path else FACTOR_LIB_PATH, dict(factor_prototypes(), **factor_dense_prototypes()))
+    lib = _open(Path(path) if path else FACTOR_LIB_PATH,
+                dict(factor_prototypes(), **factor_dense_prototypes(), **factor_graph_prototypes()))
     if lib.glove_factor_abi_version() != GLOVE_FACTOR_ABI_VERSION:
         raise GloveHipError("ABI mismatch: factor library %d, binding %d"
                             % (lib.glove_factor_abi_version(), GLOVE_FACTOR_ABI_VERSION))
     if lib.glove_factor_dense_abi_version() != GLOVE_FACTOR_DENSE_ABI_VERSION:
         raise GloveHipError("ABI mismatch: factor library (dense entry points) %d, binding %d"
                             % (lib.glove_factor_dense_abi_version(), GLOVE_FACTOR_DENSE_ABI_VERSION))
+    if lib.glove_factor_graph_abi_version() != GLOVE_FACTOR_GRAPH_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: factor library (graph entry points) %d, binding %d"
+                            % (lib.glove_factor_graph_abi_version(), GLOVE_FACTOR_GRAPH_ABI_VERSION))
     if path is None:
         _factor_lib = lib
     return lib
@@ -1640,6 +1657,39 @@ class GloveHip:
         _check(lib.glove_rows_transform_f32(_ptr(X), n, d, _ptr(T), m, _ptr(shift), _ptr(Y), _stream()),
                "glove_rows_transform_f32")
         return Y
+
+    # ---- retrofitting to a lexicon (include/glove_factor_graph_hip.h): what trainer.retrofit drives
+    def retrofit_rows(self, row_ptr: torch.Tensor, col_idx: torch.Tensor, beta: torch.Tensor | None,
+                      rows: torch.Tensor | None, Q_hat: torch.Tensor, Q_in: torch.Tensor, Q_out: torch.Tensor,
+                      alpha: float = 1.0) -> torch.Tensor:
+        """One retrofitting update of the listed rows (`rows` int32, or None: every row) of the table [n, d]:
+        Q_out[i] = (alpha w_i Q_hat[i] + sum_p beta[p] Q_in[col_idx[p]]) / (alpha w_i + w_i) over the positions p of row i
+        of the square CSR graph (row_ptr int64 [n + 1], col_idx int32 [nnz], beta float32 [nnz] or None: all 1), w_i the sum
+        of the row's weights; a listed row without positions is copied from Q_in, an unlisted one is not touched.  The
+        summation order is the header's: bitwise repeatable.  Q_out may be Q_in (the in-place sweep) when no listed row is
+        a column of another listed row — the kernel does not look; Q_out must not be Q_hat.  -> Q_out."""
+        _require(Q_hat, torch.float32); _require(Q_in, torch.float32); _require(Q_out, torch.float32)
+        if Q_hat.dim() != 2 or Q_in.shape != Q_hat.shape or Q_out.shape != Q_hat.shape:
+            raise GloveHipError("expected three tables [n, d] of one shape, got %s, %s and %s"
+                                % (tuple(Q_hat.shape), tuple(Q_in.shape), tuple(Q_out.shape)))
+        n, d = int(Q_hat.shape[0]), int(Q_hat.shape[1])
+        if n < 1 or n > 2 ** 31 - 1 or d < 4 or d > 1024 or d % 4:
+            raise GloveHipError("retrofit_rows takes 1 <= n <= 2^31 - 1 and d %% 4 == 0 in [4, 1024]: got n = %d, d = %d" % (n, d))
+        _require(row_ptr, torch.int64, n + 1); _require(col_idx, torch.int32)
+        if row_ptr is None or col_idx is None:
+            raise GloveHipError("retrofit_rows needs row_ptr and col_idx")
+        nnz = int(col_idx.numel())
+        _require(beta, torch.float32, nnz); _require(rows, torch.int32)
+        n_list = n if rows is None else int(rows.numel())
+        alpha = float(alpha)
+        if not (np.isfinite(alpha) and alpha >= 0.0):
+            raise GloveHipError("alpha must be finite and not negative, got %r" % alpha)
+        if n_list > n:
+            raise GloveHipError("%d rows listed for a table of %d" % (n_list, n))
+        _check(load_factor_library().glove_retrofit_rows_f32(_ptr(row_ptr), _ptr(col_idx), _ptr(beta), n, nnz, _ptr(rows),
+                                                             n_list, _ptr(Q_hat), _ptr(Q_in), _ptr(Q_out), d, alpha, _stream()),
+               "glove_retrofit_rows_f32")
+        return Q_out
 
     # ---- data prep
     def cooccurrence(self, tokens: torch.Tensor, V: int, context: int, cap: int | None = None):

@@ -159,10 +159,36 @@ def build_cli() -> argparse.ArgumentParser:
     return cli
 
 
-def main(argv=None, backend=None) -> dict:
+def write_step0_job_dir(output_dir, vocab, Y: np.ndarray, optimizer_name: str, extra: dict) -> dict:
+    """A job directory at step 0 around the finished vectors Y [V, width] (trainer.retrofit writes its own through this
+    too): vocab.txt, params.json the way trainer.estimator builds it, and `model.ckpt-0` with R = Y, C = 0, zero biases
+    and `optimizer_name`'s slots at their initial values; `extra` goes into the checkpoint beside the tables.
+    -> the params that were written."""
     from trainer.config_utils import build_parser, init_params
-    from trainer.data_utils import read_vocab
     from trainer.hip_api import DeviceTables
+    from trainer.train_utils import CheckpointManager, get_optimizer
+    optimizer = get_optimizer(optimizer_name)["class_name"]
+    job = Path(output_dir)
+    job.mkdir(parents=True, exist_ok=True)
+    vocab_txt = job / "vocab.txt"
+    vocab_txt.write_bytes("\n".join(vocab).encode("utf8"))
+    V, width = Y.shape
+    # params.json the way trainer.estimator builds it: its parser's defaults under the flags the two commands share
+    params = vars(build_parser().parse_args([
+        "--vocab-txt", str(vocab_txt), "--job-dir", str(job), "--disable-datetime-path", "--embedding-size", str(width),
+        "--optimizer", optimizer_name])).copy()
+    params = init_params(params)
+    new = DeviceTables(V, width, optimizer, device="cpu", seed=0)           # slots and scalars at step 0
+    new.embeddings("R").copy_(torch.from_numpy(Y.astype(np.float32)))
+    new.embeddings("C").zero_()
+    new.br.zero_()
+    new.bc.zero_()
+    CheckpointManager(params["job_dir"]).save(new, extra=extra)
+    return params
+
+
+def main(argv=None, backend=None) -> dict:
+    from trainer.data_utils import read_vocab
     from trainer.train_utils import CheckpointManager, get_optimizer
     args = build_cli().parse_args(argv)
     optimizer = get_optimizer(args.optimizer)["class_name"]
@@ -190,27 +216,13 @@ def main(argv=None, backend=None) -> dict:
     out = postprocess_table(W.float(), remove, args.reduce_to, center=not args.no_center, backend=backend)
     seconds.update(out["seconds"])
     t0 = time.perf_counter()
-    job = Path(args.output_dir)
-    job.mkdir(parents=True, exist_ok=True)
-    vocab_txt = job / "vocab.txt"
-    vocab_txt.write_bytes("\n".join(vocab).encode("utf8"))
     V, width = out["Y"].shape
-    # params.json the way trainer.estimator builds it: its parser's defaults under the flags the two commands share
-    params = vars(build_parser().parse_args([
-        "--vocab-txt", str(vocab_txt), "--job-dir", str(job), "--disable-datetime-path", "--embedding-size", str(width),
-        "--optimizer", args.optimizer])).copy()
-    params = init_params(params)
-    new = DeviceTables(V, width, optimizer, device="cpu", seed=0)           # slots and scalars at step 0
-    new.embeddings("R").copy_(torch.from_numpy(out["Y"].astype(np.float32)))
-    new.embeddings("C").zero_()
-    new.br.zero_()
-    new.bc.zero_()
     record = {"source_job_dir": str(source["job_dir"]), "source_step": int(tables["global_step"]), "embeddings": args.embeddings,
               "remove_components": remove, "reduce_to": args.reduce_to, "center": not args.no_center,
               "restrict_vocab": args.restrict_vocab, "optimizer": optimizer, "vocab_size": V, "source_embedding_size": d_model,
               "embedding_size": width, "top_eigenvalues": [float(x) for x in out["eigenvalues"][:TOP_EIGENVALUES]],
               "variance_removed": out["variance_removed"], "variance_kept": out["variance_kept"]}
-    CheckpointManager(params["job_dir"]).save(new, extra={"postprocess": record})
+    params = write_step0_job_dir(args.output_dir, vocab, out["Y"], args.optimizer, {"postprocess": record})
     seconds["write_job_dir"] = time.perf_counter() - t0
     Path(params["job_dir"], "postprocess.json").write_text(json.dumps(dict(record, seconds=seconds), indent=2))
     logger.info("%d x %d (%s of %s, step %d): %d components removed (%.3g of the variance), %d columns kept -> %s", V, d_model,
