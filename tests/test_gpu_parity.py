@@ -1138,7 +1138,8 @@ def test_lists_of_several_ranks_sum_in_rank_order(hip, B, V, d, W, count_first):
     """W virtual ranks on one GPU, each with its own batch: their packed lists combined in rank order == the dense
     buffer they would have all-reduced (dense_grad of every plan into one G, in rank order), bit for bit, and both
     match the float64 oracle on the joint batch.  `count_first`: glove_count_packed_f32 ahead of the combines (ids that one
-    list alone touches are then applied straight from their entry and skip the dense buffer) — the same bits."""
+    list alone touches are then applied straight from their entry and skip the dense buffer) — the same bits.
+    (Every row shape, every kind of list and lists longer than one grid sweep: tests/test_gpu_exchange_row_shapes.py.)"""
     from trainer.hip_api import DeviceTables, make_hyper
     t = oracle_tables(V, d, "Adagrad")
     a, b = tables_from_oracle(t, DeviceTables), tables_from_oracle(t, DeviceTables)

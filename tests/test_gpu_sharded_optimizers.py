@@ -1,6 +1,7 @@
 """The sharded multi-GPU forms under every Keras optimizer, on the GPU: the touched-rows apply of the dense-decay optimizers
 (Adam, RMSprop, Nadam) restricted to one side against the float64 oracle, the sharded steppers alone in the world against the
-plain single-GPU step, every form through RCCL with one rank, and the CLI with two ranks on the one GPU."""
+plain single-GPU step, every form through RCCL with one rank, and the CLI with two ranks on the one GPU.
+(The same apply at every row shape, on lists of several ranks and on lists longer than one grid sweep: tests/test_gpu_exchange_row_shapes.py.)"""
 import json
 import sys
 from pathlib import Path
