@@ -33,6 +33,7 @@ GLOVE_ABI_VERSION = 15
 GLOVE_EVAL_ABI_VERSION = 1
 GLOVE_EVAL_SIM_ABI_VERSION = 1      # include/glove_eval_sim_hip.h: the same library's second header, versioned on its own
 GLOVE_EVAL_CLUSTER_ABI_VERSION = 1  # include/glove_eval_cluster_hip.h: the third header (spherical k-means), likewise
+GLOVE_EVAL_CROSS_ABI_VERSION = 1    # include/glove_eval_cross_hip.h: the fourth header (neighbours across two tables, CSLS), likewise
 GLOVE_COOC_STREAM_ABI_VERSION = 1   # include/glove_cooc_stream_hip.h (libglove_prep_hip.so)
 COOC_MERGE_TILE = 2048              # GLOVE_COOC_MERGE_TILE: merged positions one workgroup of glove_cooc_merge_u64 owns
 GLOVE_TEXT_ABI_VERSION = 1          # include/glove_text_hip.h: the same library's second header (tokenizing), versioned on its own
@@ -54,6 +55,7 @@ GLOVE_FACTOR_DENSE_ABI_VERSION = 1  # include/glove_factor_dense_hip.h: the same
 GRAM_CHUNK = 1024                   # GLOVE_GRAM_CHUNK: rows of one float32 fmaf chain of glove_gram_f64
 GRAM_SLICE = 16384                  # GLOVE_GRAM_SLICE: rows whose chunk partials one float64 slice partial adds
 GLOVE_FACTOR_GRAPH_ABI_VERSION = 1  # include/glove_factor_graph_hip.h: the same library's third header (retrofitting), versioned on its own
+GLOVE_FACTOR_ALIGN_ABI_VERSION = 1  # include/glove_factor_align_hip.h: the same library's fourth header (cross-covariance of row pairs), versioned on its own
 REWEIGHT_KINDS = {"none": 0, "sqrt": 1, "log1p": 2, "ppmi": 3}      # GLOVE_REWEIGHT_*
 HEAD_REGRESSION, HEAD_LOGISTIC = 0, 1      # glove_hyper.head
 OPTIMIZER_CODES = {o.name: o.code for o in OPTIMIZERS.values()}      # glove_hyper.optimizer (GLOVE_OPT_*): trainer/optimizers.py holds what every name needs
@@ -104,6 +106,9 @@ EVAL_SIM_EXPORTED_SYMBOLS = ("glove_eval_sim_abi_version", "glove_cosmul_workspa
 EVAL_CLUSTER_EXPORTED_SYMBOLS = ("glove_eval_cluster_abi_version", "glove_kmeans_workspace_bytes", "glove_kmeans_assign_f32",
                                  "glove_kmeans_update_f32")
 KMEANS_MAX_CLUSTERS = 4096
+# every symbol include/glove_eval_cross_hip.h declares (the same library)
+EVAL_CROSS_EXPORTED_SYMBOLS = ("glove_eval_cross_abi_version", "glove_cross_topk_workspace_bytes", "glove_cross_topk_f32",
+                               "glove_topk_mean_f32")
 # every symbol include/glove_cooc_stream_hip.h declares (libglove_prep_hip.so)
 PREP_EXPORTED_SYMBOLS = ("glove_cooc_stream_abi_version", "glove_cooc_chunk_workspace_bytes", "glove_cooc_chunk_keys_i32",
                          "glove_cooc_merge_workspace_bytes", "glove_cooc_merge_u64", "glove_cooc_finalize_workspace_bytes",
@@ -130,6 +135,8 @@ FACTOR_DENSE_EXPORTED_SYMBOLS = ("glove_factor_dense_abi_version", "glove_gram_w
                                  "glove_gram_f64", "glove_rows_transform_f32")
 # every symbol include/glove_factor_graph_hip.h declares (the same library)
 FACTOR_GRAPH_EXPORTED_SYMBOLS = ("glove_factor_graph_abi_version", "glove_retrofit_rows_f32")
+# every symbol include/glove_factor_align_hip.h declares (the same library)
+FACTOR_ALIGN_EXPORTED_SYMBOLS = ("glove_factor_align_abi_version", "glove_cross_gram_workspace_bytes", "glove_cross_gram_f64")
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -258,8 +265,20 @@ def load_library(path: os.PathLike | None = None, any_abi: bool = False) -> C.CD
 _eval_lib = None
 
 
+def eval_cross_prototypes() -> dict:
+    """name -> (result, arguments) of every function include/glove_eval_cross_hip.h declares."""
+    sz, i32, vp = C.c_size_t, C.c_int32, C.c_void_p
+    return {
+        "glove_eval_cross_abi_version": (C.c_int, []),
+        "glove_cross_topk_workspace_bytes": (sz, [i32, i32, i32, i32]),
+        "glove_cross_topk_f32": (C.c_int, [vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+        "glove_topk_mean_f32": (C.c_int, [vp, i32, i32, vp, vp]),
+    }
+
+
 def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
-    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h, include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h) and declare the prototypes, at the first call that needs it:
+    """dlopen libglove_eval_hip.so (include/glove_eval_hip.h, include/glove_eval_sim_hip.h, include/glove_eval_cluster_hip.h,
+    include/glove_eval_cross_hip.h) and declare the prototypes, at the first call that needs it:
     training never loads it.  Raises if it is not built, like load_library."""
     global _eval_lib
     if _eval_lib is not None and path is None:
@@ -278,6 +297,7 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
         "glove_kmeans_assign_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, i32, vp, vp, vp, sz, vp]),
         "glove_kmeans_update_f32": (C.c_int, [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp, sz, vp]),
     }
+    protos.update(eval_cross_prototypes())
     lib = _open(Path(path) if path else EVAL_LIB_PATH, protos)
     if lib.glove_eval_abi_version() != GLOVE_EVAL_ABI_VERSION:
         raise GloveHipError("ABI mismatch: eval library %d, binding %d" % (lib.glove_eval_abi_version(), GLOVE_EVAL_ABI_VERSION))
@@ -287,6 +307,9 @@ def load_eval_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_eval_cluster_abi_version() != GLOVE_EVAL_CLUSTER_ABI_VERSION:
         raise GloveHipError("ABI mismatch: eval library (clustering entry points) %d, binding %d"
                             % (lib.glove_eval_cluster_abi_version(), GLOVE_EVAL_CLUSTER_ABI_VERSION))
+    if lib.glove_eval_cross_abi_version() != GLOVE_EVAL_CROSS_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: eval library (cross-table entry points) %d, binding %d"
+                            % (lib.glove_eval_cross_abi_version(), GLOVE_EVAL_CROSS_ABI_VERSION))
     if path is None:
         _eval_lib = lib
     return lib
@@ -394,15 +417,26 @@ def factor_graph_prototypes() -> dict:
     }
 
 
+def factor_align_prototypes() -> dict:
+    """name -> (result, arguments) of every function include/glove_factor_align_hip.h declares."""
+    sz, i32, i64, vp = C.c_size_t, C.c_int32, C.c_int64, C.c_void_p
+    return {
+        "glove_factor_align_abi_version": (C.c_int, []),
+        "glove_cross_gram_workspace_bytes": (sz, [i64, i32]),
+        "glove_cross_gram_f64": (C.c_int, [vp, i32, vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, sz, vp]),
+    }
+
+
 def load_factor_library(path: os.PathLike | None = None) -> C.CDLL:
     """dlopen libglove_factor_hip.so (include/glove_factor_hip.h, include/glove_factor_dense_hip.h,
-    include/glove_factor_graph_hip.h) and declare the
+    include/glove_factor_graph_hip.h, include/glove_factor_align_hip.h) and declare the
     prototypes, at the first call that needs it: training never loads it.  Raises if it is not built, like load_library."""
     global _factor_lib
     if _factor_lib is not None and path is None:
         return _factor_lib
     lib = _open(Path(path) if path else FACTOR_LIB_PATH,
-                dict(factor_prototypes(), **factor_dense_prototypes(), **factor_graph_prototypes()))
+                dict(factor_prototypes(), **factor_dense_prototypes(), **factor_graph_prototypes(),
+                     **factor_align_prototypes()))
     if lib.glove_factor_abi_version() != GLOVE_FACTOR_ABI_VERSION:
         raise GloveHipError("ABI mismatch: factor library %d, binding %d"
                             % (lib.glove_factor_abi_version(), GLOVE_FACTOR_ABI_VERSION))
@@ -412,6 +446,9 @@ def load_factor_library(path: os.PathLike | None = None) -> C.CDLL:
     if lib.glove_factor_graph_abi_version() != GLOVE_FACTOR_GRAPH_ABI_VERSION:
         raise GloveHipError("ABI mismatch: factor library (graph entry points) %d, binding %d"
                             % (lib.glove_factor_graph_abi_version(), GLOVE_FACTOR_GRAPH_ABI_VERSION))
+    if lib.glove_factor_align_abi_version() != GLOVE_FACTOR_ALIGN_ABI_VERSION:
+        raise GloveHipError("ABI mismatch: factor library (alignment entry points) %d, binding %d"
+                            % (lib.glove_factor_align_abi_version(), GLOVE_FACTOR_ALIGN_ABI_VERSION))
     if path is None:
         _factor_lib = lib
     return lib
@@ -1456,6 +1493,49 @@ class GloveHip:
         _check(lib.glove_pair_cosine_f32(_ptr(W), V, d, _ptr(pairs), n, _ptr(out), _stream()), "glove_pair_cosine_f32")
         return out
 
+    # ---- neighbours across two tables, by cosine or CSLS (include/glove_eval_cross_hip.h): what trainer.align drives
+    def cross_topk(self, Q: torch.Tensor, qid: torch.Tensor, T: torch.Tensor, k: int, q_pen: torch.Tensor | None = None,
+                   t_pen: torch.Tensor | None = None, batch: int = 1024):
+        """For the rows qid [n] of Q [Vq, d] the k rows of T [Vt, d] with the largest cosine -> (scores, idx) [n, k],
+        descending, ties to the lower id; with q_pen [n] and t_pen [Vt] (both or neither) the score is CSLS's
+        2 cos - q_pen[q] - t_pen[v].  The scores of `batch` queries are a [batch, Vt] matrix in the workspace: the queries
+        are walked in batches of that size through one workspace, and a query's result does not depend on its batch.  The
+        ids must lie in [0, Vq): the kernels do not look."""
+        _require(Q, torch.float32); _require(T, torch.float32); _require(qid, torch.int32)
+        if Q.dim() != 2 or T.dim() != 2 or qid.dim() != 1 or Q.shape[1] != T.shape[1]:
+            raise GloveHipError("expected Q [Vq, d], T [Vt, d] of one row stride and qid [n]")
+        if batch < 1:
+            raise GloveHipError("batch must be positive, got %d" % batch)
+        if (q_pen is None) != (t_pen is None):
+            raise GloveHipError("CSLS takes both penalty arrays, nearest neighbours neither")
+        lib = load_eval_library()
+        (Vq, d), Vt, n = Q.shape, int(T.shape[0]), int(qid.numel())
+        _require(q_pen, torch.float32, n); _require(t_pen, torch.float32, Vt)
+        sims = torch.empty(n, k, dtype=torch.float32, device=Q.device)
+        idx = torch.empty(n, k, dtype=torch.int32, device=Q.device)
+        ws = torch.empty(max(lib.glove_cross_topk_workspace_bytes(min(batch, n), Vt, d, k), 256), dtype=torch.uint8, device=Q.device)
+        for s in range(0, max(n, 1), batch):      # (n == 0: one call, which checks the sizes and launches nothing)
+            m = min(batch, n - s)
+            _check(lib.glove_cross_topk_f32(_ptr(Q), Vq, _ptr(qid[s:s + m]), m, _ptr(T), Vt, d, k,
+                                            None if q_pen is None else _ptr(q_pen[s:s + m]), _ptr(t_pen), _ptr(sims[s:s + m]),
+                                            _ptr(idx[s:s + m]), _ptr(ws), ws.numel(), _stream()), "glove_cross_topk_f32")
+        return sims, idx
+
+    def topk_mean(self, sims: torch.Tensor) -> torch.Tensor:
+        """The mean of each row of sims [n, k] -> [n]: a float32 sum in position order, one division by k."""
+        _require(sims, torch.float32)
+        if sims.dim() != 2 or sims.shape[1] < 1:
+            raise GloveHipError("expected sims [n, k >= 1], got %s" % (tuple(sims.shape),))
+        lib = load_eval_library()
+        n, k = int(sims.shape[0]), int(sims.shape[1])
+        out = torch.empty(n, dtype=torch.float32, device=sims.device)
+        _check(lib.glove_topk_mean_f32(_ptr(sims), n, k, _ptr(out), _stream()), "glove_topk_mean_f32")
+        return out
+
+    def csls_penalty(self, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, knn: int = 10, batch: int = 1024) -> torch.Tensor:
+        """The mean cosine of each row A[ids] to its `knn` nearest rows of B -> [n]: topk_mean of cross_topk's scores."""
+        return self.topk_mean(self.cross_topk(A, ids, B, knn, batch=batch)[0])
+
     # ---- spherical k-means (include/glove_eval_cluster_hip.h)
     def _kmeans_args(self, W, ids, centroids, assign=None):
         _require(W, torch.float32); _require(ids, torch.int32); _require(centroids, torch.float32)
@@ -1657,6 +1737,30 @@ class GloveHip:
         _check(lib.glove_rows_transform_f32(_ptr(X), n, d, _ptr(T), m, _ptr(shift), _ptr(Y), _stream()),
                "glove_rows_transform_f32")
         return Y
+
+    # ---- the cross-covariance of row pairs (include/glove_factor_align_hip.h): what trainer.align fits its map on
+    def cross_gram(self, X: torch.Tensor, xid: torch.Tensor, Y: torch.Tensor, yid: torch.Tensor,
+                   x_scale: torch.Tensor | None = None, y_scale: torch.Tensor | None = None,
+                   ws: torch.Tensor | None = None) -> torch.Tensor:
+        """M [d, d] float64 = sum over the pairs p of the outer product of X[xid[p]] x_scale[xid[p]] and
+        Y[yid[p]] y_scale[yid[p]] (float32 products; a null scale leaves the row as it is) for X [Vx, d] and Y [Vy, d]
+        float32 of one row stride: float32 fmaf chains over chunks of GRAM_CHUNK pairs, added in float64.  Bitwise
+        repeatable (no float atomics).  The ids must lie in [0, Vx) and [0, Vy): the kernels do not look."""
+        _require(X, torch.float32); _require(Y, torch.float32); _require(xid, torch.int32)
+        if X.dim() != 2 or Y.dim() != 2 or X.shape[1] != Y.shape[1] or xid.dim() != 1:
+            raise GloveHipError("cross_gram: expected X [Vx, d], Y [Vy, d] of one row stride and xid, yid [n]")
+        (Vx, d), Vy, n = X.shape, int(Y.shape[0]), int(xid.numel())
+        _require(yid, torch.int32, n)
+        _require(x_scale, torch.float32, Vx); _require(y_scale, torch.float32, Vy)
+        lib = load_factor_library()
+        need = lib.glove_cross_gram_workspace_bytes(n, d)
+        if need == 0 or Vx < 1 or Vy < 1:
+            raise GloveHipError("cross_gram takes 1 <= n <= 2^31 - 1 pairs and d %% 4 == 0 in [4, 1024]: got n = %d, d = %d" % (n, d))
+        ws = torch.empty(need, dtype=torch.uint8, device=X.device) if ws is None else ws
+        M = torch.empty(d, d, dtype=torch.float64, device=X.device)
+        _check(lib.glove_cross_gram_f64(_ptr(X), Vx, _ptr(Y), Vy, d, _ptr(xid), _ptr(yid), n, _ptr(x_scale), _ptr(y_scale),
+                                        _ptr(M), _ptr(ws), ws.numel(), _stream()), "glove_cross_gram_f64")
+        return M
 
     # ---- retrofitting to a lexicon (include/glove_factor_graph_hip.h): what trainer.retrofit drives
     def retrofit_rows(self, row_ptr: torch.Tensor, col_idx: torch.Tensor, beta: torch.Tensor | None,
